@@ -4,12 +4,16 @@ Headline (value): PageRank fp64 on RMAT scale-24 edgefactor-16 (BASELINE.json co
 "step" = one power superstep of JanusGraph's PageRankVertexProgram over the whole graph (pull SpMV
 over the in-CSR + contribution write + RCCL allgather of the rank-contribution vector when N > 1).
 value = directed edges processed per second over all GPUs (GTEPS), inputs resident in HBM.
-Secondary blocks (same JSON line, one GPU): "bfs" = DO-BFS (SPVP depth, undirected) from one source on
+A plain run does the headline only: build the graph, warm up, time the K supersteps (their roofline comes
+from HIP events of those same supersteps), print the line.  --dump-outputs DIR also writes what the last
+timed superstep left for the caller (jg_pagerank_end's rank and edge count) as DIR/<name>.npy.
+--full adds the secondary blocks (same JSON line, one GPU): the headline's CPU baseline and "required"
+roofline; "bfs" = DO-BFS (SPVP depth, undirected) from one source on
 RMAT scale-20 (configs[1]) as Graph500 TEPS with its roofline and CPU baseline; "rmat26" = PageRank
 (with roofline), DO-BFS, ConnectedComponent (configs[3]) and 64-source MS-BFS (configs[4]) at scale 26.
 With N > 1: "per_rank" = each rank's superstep kernel time, exchange time, halo volume and roofline.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
       N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -65,6 +69,11 @@ def parse():
     p.add_argument("--scale", type=int, default=24)
     p.add_argument("--edgefactor", type=int, default=16)
     p.add_argument("--seed", type=int, default=0x5EED + 24)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the secondary blocks (CPU baselines, the RMAT-20 BFS, the "
+                        "RMAT-26 blocks, the 'required' roofline); --no-bfs / --no-cpu / --no-big pick among them")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the outputs of the last timed superstep (rank, edge_count) to DIR/<name>.npy")
     p.add_argument("--bfs-scale", type=int, default=20)
     p.add_argument("--no-bfs", action="store_true")
     p.add_argument("--no-cpu", action="store_true")
@@ -80,7 +89,27 @@ def parse():
     p.add_argument("--host-transport", action="store_true",
                    help="N > 1 rehearsal on one GPU: every rank on device 0, exchanges over gloo through the "
                         "library's host transport instead of RCCL (not a performance measurement)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps needs at least 1 timed superstep and --warmup 0 or more")
+    return args
+
+
+DUMP_MAX_VALUES = 3 << 20  # per array: two float64 arrays of 3 Mi values = 48 MiB, under the 64 MB a dump may take
+
+
+def dump_outputs(outdir, arrays, suffix=""):
+    """Write each array (float64, one value per vertex) as outdir/<name><suffix>.npy.  An array longer than
+    DUMP_MAX_VALUES is cut to the same fixed, seeded sample of its indices (sorted) in every run, so two
+    builds given the same arguments write comparable files."""
+    os.makedirs(outdir, exist_ok=True)
+    sample = {}
+    for name, a in arrays.items():
+        if len(a) > DUMP_MAX_VALUES:
+            if len(a) not in sample:
+                sample[len(a)] = np.sort(np.random.default_rng(0xD0).choice(len(a), DUMP_MAX_VALUES, replace=False))
+            a = a[sample[len(a)]]
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, np.float64))
 
 
 def dist_env():
@@ -551,7 +580,9 @@ def main():
     g = ctx.build_rmat(args.scale, args.edgefactor, args.seed, flags=jg.ADJ_IN)
     build_ms = ctx.stats()["build_ms"]
     info = g.info()
-    live = int(ctl.sum(float(np.count_nonzero(g.degrees(jg.DIR_IN)))))  # rows with an in-edge, all ranks
+    live = None
+    if args.full and ws == 1:
+        live = int(np.count_nonzero(g.degrees(jg.DIR_IN)))  # rows with an in-edge ("required" roofline)
     g.pagerank_begin(0.85, n)
     g.pagerank_step(args.warmup)
     g.sync()
@@ -565,9 +596,12 @@ def main():
     window_end(f"pagerank_fp64_rmat{args.scale}_ef{args.edgefactor}", w0, args.steps)
     ctl.barrier()
     elapsed = ctl.max(t1 - t0)
-    g.pagerank_end(want=False)
+    rank_out, edge_count = g.pagerank_end(want=bool(args.dump_outputs))
     st = ctx.stats()
     ctx.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rank": rank_out, "edge_count": edge_count}, "" if ws == 1 else f"_r{rank}")
+        del rank_out, edge_count
     ms_per_step = elapsed / args.steps * 1e3
     value = m * args.steps / elapsed / 1e9  # GTEPS, all ranks
 
@@ -582,7 +616,7 @@ def main():
     workload = f"pagerank_fp64_rmat{args.scale}_ef{args.edgefactor}"
     roofline = hbm_roofline(alg_bytes_launch, kern_ms, "PageRank superstep (pull_merge_kernel x bands + fixup + "
                             "fused light-row/finalize kernel, PrOp)", workload if ws == 1 else None, PR_MODEL)
-    if ws == 1:
+    if live is not None:
         roofline["required"] = required_roofline(m, live, kern_ms)
     per_rank = None
     if ws > 1:
@@ -596,10 +630,10 @@ def main():
     g.close()
 
     extra = {}
-    if not args.no_bfs and ws == 1:
+    if args.full and not args.no_bfs and ws == 1:
         extra["bfs"] = bfs_block(jg, ctx, ctl, args.bfs_scale, args.edgefactor, cpu=not args.no_cpu,
                                  cpu_seconds=args.cpu_seconds)
-    if not args.no_big:
+    if args.full and not args.no_big:
         # N > 1: the configs[3] / [4] workloads on N GPUs (sharded DO-BFS, CC propagation, sharded MS-BFS)
         big = args.big_scale
         blk = {}
@@ -611,7 +645,7 @@ def main():
         extra[f"rmat{big}"] = blk
 
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu:
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu:
         cpu = cpu_baseline(args.scale, args.edgefactor, args.seed, args.cpu_seconds)
 
     if rank == 0:
@@ -619,7 +653,7 @@ def main():
             "metric": "GTEPS for PageRank iter + BFS, RMAT-24/26, 1/2/4/8 GPUs; % of HBM peak",
             "value": round(value, 3), "unit": "GTEPS", "n_gpus": ws, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic (Graph500 Kronecker RMAT, on-device generator)",
+            "vs_baseline": None, "dtype": "f64", "full": args.full, "data": "synthetic (Graph500 Kronecker RMAT, on-device generator)",
             "config": {"workload": workload, "n": n, "m": m,
                        "parallelism": (f"1d-vertex-partition x{ws}, " + ("host-transport rehearsal on one GPU (not a "
                                        "measurement)" if args.host_transport else "RCCL halo send/recv"))

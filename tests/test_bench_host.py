@@ -99,6 +99,33 @@ def test_roofline_reports_fabric_fraction_beside_the_model():
     assert "frac_fabric" not in bench.hbm_roofline(1e9, 1.0, "k")
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a short array is written whole as float64; a long one is cut to the same sorted index
+    sample in every call, so two runs' files compare value for value, and a dump stays under 64 MB."""
+    small = np.arange(10, dtype=np.float64) / 3
+    big = np.arange(bench.DUMP_MAX_VALUES + 7, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"rank": small, "edge_count": big})
+    bench.dump_outputs(str(tmp_path / "b"), {"edge_count": big + 0.5}, "_r1")
+    got = np.load(tmp_path / "a" / "rank.npy")
+    assert got.dtype == np.float64 and (got == small).all()
+    a, b = np.load(tmp_path / "a" / "edge_count.npy"), np.load(tmp_path / "b" / "edge_count_r1.npy")
+    assert a.dtype == np.float64 and len(a) == bench.DUMP_MAX_VALUES and (np.diff(a) > 0).all()
+    assert (b == a + 0.5).all()  # the same indices both times (big holds its own indices)
+    assert 2 * os.path.getsize(tmp_path / "a" / "edge_count.npy") <= 64e6
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert not args.full and args.dump_outputs is None and args.steps == 3 and args.warmup == 1
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_code_identity(monkeypatch):
     """The bench line names what it measured: JG_BENCH_HEAD (the GPU box gets the tree without .git) and
     content hashes of bench.py and the library (bench_trace.py copies both into its summary)."""

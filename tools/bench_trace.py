@@ -2,7 +2,7 @@
 item 5).  Run the bench under the profiler with its timed regions' host-clock windows in the JSON line:
 
     JG_TRACE_MARKS=1 rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o bench -- python3 bench.py \
-        --gpus 1 --steps 20 --warmup 5 --trace-windows > OUT/bench.json
+        --gpus 1 --steps 20 --warmup 5 --full --trace-windows > OUT/bench.json
     python tools/bench_trace.py OUT bench OUT/bench.json [--out profiles/r05/bench_trace/summary.json]
 
 Each window (a block's timed call, or the K supersteps of a PageRank block) selects the dispatches that

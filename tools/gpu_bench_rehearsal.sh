@@ -12,6 +12,6 @@ export TMPDIR=/tmp
 for N in 2 8; do
   extra=""
   [ $N = 8 ] && extra="--cc-plan sharded"
-  timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 3 --warmup 1 --host-transport --no-cpu $extra > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err || exit 3
+  timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) bench.py --gpus $N --steps 3 --warmup 1 --full --host-transport --no-cpu $extra > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err || exit 3
 done
 echo ok
