@@ -210,28 +210,17 @@ __global__ __launch_bounds__(kBlock) void cc_push_kernel(CcPush a) {
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x) * 4 >= a.mf) break;  // block-uniform
         const int64_t e0 = (t * nthreads + tid) * 4;
-        int64_t i = 0, next_bound = 0;
-        if (e0 < a.mf) {
-            int64_t lo = 0, hi = a.nq - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (a.qoff[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            i = lo;
-            next_bound = i + 1 < a.nq ? a.qoff[i + 1] : a.mf;
-        }
+        EdgeCursor cur{a.qoff, a.nq, a.mf};
+        if (e0 < a.mf) cur.seek(e0);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int64_t e = e0 + k;
             bool take = false;
             int32_t v = 0;
             if (e < a.mf) {
-                while (e >= next_bound) {
-                    ++i;
-                    next_bound = i + 1 < a.nq ? a.qoff[i + 1] : a.mf;
-                }
-                const int32_t u = a.queue[i];
-                v = a.col[a.rp[u] + (e - a.qoff[i])];
+                cur.advance(e);
+                const int32_t u = a.queue[cur.i];
+                v = a.col[a.rp[u] + cur.row_offset(e)];
                 const int32_t m = a.msg[u];
                 if (m < a.cand[v]) take = atomicMin(&a.cand[v], m) == kNoMsg;
             }
@@ -1684,9 +1673,7 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out) {
     any = allreduce_or(g, any);
 
     DeviceGuard dg0(sh0.device);
-    hipEvent_t t0, t1;
-    JG_HIP(hipEventCreate(&t0));
-    JG_HIP(hipEventCreate(&t1));
+    Event t0, t1;
     const bool uf_one = g.shards.size() == 1 && g.P == 1 && tune().cc_uf;
     if (uf_one && sh0.rows > 0) {  // the union-find path's scratch
         if ((int64_t)sh0.cc_depth.size() < sh0.rows) sh0.cc_depth.alloc(sh0.rows);
@@ -1840,8 +1827,6 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out) {
     JG_HIP(hipEventSynchronize(t1));
     float ms = 0;
     JG_HIP(hipEventElapsedTime(&ms, t0, t1));
-    JG_HIP(hipEventDestroy(t0));
-    JG_HIP(hipEventDestroy(t1));
     ctx.last.compute_ms = ms;
     ctx.last.supersteps = iteration;
     ctx.last.levels = iteration;

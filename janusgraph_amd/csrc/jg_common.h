@@ -183,4 +183,19 @@ struct DeviceGuard {
     }
 };
 
+// Owning HIP event, created on the current device or on `device`.  The entry points time their regions with a pair of
+// these: fail() throws, and an event destroyed by hand at the end of the function leaked on every error.
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() { JG_HIP(hipEventCreate(&ev)); }
+    explicit Event(int device) {
+        DeviceGuard dg(device);
+        JG_HIP(hipEventCreate(&ev));
+    }
+    ~Event() { (void)hipEventDestroy(ev); }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    operator hipEvent_t() const { return ev; }
+};
+
 }  // namespace jg

@@ -1,4 +1,5 @@
-// jg_frontier.h — frontier queues shared by the traversals (jg_traverse.hip) and CC (jg_cc.hip).
+// jg_frontier.h — frontier queues, and the walk over their edges, shared by the traversals
+// (jg_traverse.hip, jg_narrow.hip) and CC (jg_cc.hip).
 #pragma once
 
 #include "jg_prim.h"
@@ -129,5 +130,74 @@ struct WaveApp {
     }
     __device__ void final(int32_t* q, int64_t* qo, unsigned long long* packed) { wave_stage_final(sa, run, q, qo, packed); }
 };
+
+// Edge-parallel walk over a frontier.  A queue of nq entries carries each entry's first edge number
+// (qoff, monotone; mf edges in all), so frontier edge e in [0, mf) belongs to the entry i with
+// qoff[i] <= e < qoff[i + 1].  A thread finds the entry of its first edge once (seek) and steps on while
+// it takes consecutive edges (advance).  Zero-degree entries share their successor's offset: the search
+// returns the last of them and the step skips them.  The tile loops around the walk (grid shape, which
+// threads leave early, edges per thread) differ between the kernels and stay with them.
+struct EdgeCursor {
+    const int64_t* qoff;
+    int64_t nq, mf;
+    int64_t i = 0, next_bound = 0;  // the current entry; the first edge past it
+    __device__ __forceinline__ void seek_entry(int64_t entry) {
+        i = entry;
+        next_bound = i + 1 < nq ? qoff[i + 1] : mf;
+    }
+    // the entry of edge e0 < mf, by binary search over qoff[0, nq)
+    __device__ __forceinline__ void seek(int64_t e0) {
+        int64_t lo = 0, hi = nq - 1;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (qoff[mid] <= e0) lo = mid; else hi = mid - 1;
+        }
+        seek_entry(lo);
+    }
+    // on to the entry of edge e (at or past the last edge sought)
+    __device__ __forceinline__ void advance(int64_t e) {
+        while (e >= next_bound) {  // skips zero-degree entries too
+            ++i;
+            next_bound = i + 1 < nq ? qoff[i + 1] : mf;
+        }
+    }
+    // e's position in its entry's adjacency row
+    __device__ __forceinline__ int64_t row_offset(int64_t e) const { return e - qoff[i]; }
+};
+
+// The search over LDS samples: every stride-th edge offset of the queue (stride = ceil(nq / kQoffSamples))
+// is staged in LDS by each block with work, the search runs there and then over at most `stride` global
+// offsets.  The offsets were appended by every XCD in the previous launch, so each global probe misses
+// the reading XCD's L2: a 22.6 K-entry queue cost 15 dependent probes (RMAT-20 level 4, a 24.9 K-entry
+// top-down level: 12.4 us).
+constexpr int kQoffSamples = 1024;
+struct QoffIndex {
+    const int64_t* lds;  // samples: lds[j] = qoff[j * stride]
+    int64_t stride, count;
+};
+// Block-uniform call (it ends in a barrier); s_qs: kQoffSamples words of LDS; ept: edges per thread.
+__device__ __forceinline__ QoffIndex stage_qoff(const int64_t* qoff, int64_t nq, int64_t mf, int ept, int64_t* s_qs) {
+    QoffIndex q{s_qs, (nq + kQoffSamples - 1) / kQoffSamples, 0};
+    if (q.stride < 1) q.stride = 1;  // an empty queue
+    q.count = (nq + q.stride - 1) / q.stride;
+    if ((int64_t)blockIdx.x * blockDim.x * ept < mf)  // block-uniform: blocks past the frontier's edges skip it
+        for (int64_t j = threadIdx.x; j < q.count; j += blockDim.x) s_qs[j] = qoff[j * q.stride];
+    __syncthreads();
+    return q;
+}
+// the entry of edge e < mf (as EdgeCursor::seek)
+__device__ __forceinline__ int64_t find_entry(const int64_t* qoff, const QoffIndex& q, int64_t nq, int64_t e) {
+    int64_t lo = 0, hi = q.count - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (q.lds[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    int64_t g0 = lo * q.stride, g1 = (g0 + q.stride < nq ? g0 + q.stride : nq) - 1;
+    while (g0 < g1) {
+        const int64_t mid = (g0 + g1 + 1) >> 1;
+        if (qoff[mid] <= e) g0 = mid; else g1 = mid - 1;
+    }
+    return g0;
+}
 
 }  // namespace jg

@@ -30,7 +30,6 @@ namespace {
 constexpr int kNbRing = 4;         // per-level state / counters: a level touches slots L-1, L, L+1
 constexpr int kNbStep = 256;       // pass B: entries a wave scans per step (4 per lane)
 constexpr int kNbEpt = 4;          // top-down: edges per thread beyond the grid
-constexpr int kNbSamples = 1024;   // top-down: LDS samples of the queue's edge offsets
 
 // Counters of the frontier a level produces (zeroed two levels ahead by the first kernel's block 0)
 struct NbCtr {
@@ -311,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void nb_scan_kernel(NbLevel a) {
 // in a byte queues the row for the next level.
 __global__ __launch_bounds__(kBlock) void nb_td_kernel(NbLevel a) {
     __shared__ WaveStage s_app;
-    __shared__ int64_t s_qs[kNbSamples];
+    __shared__ int64_t s_qs[kQoffSamples];
     __shared__ unsigned long long s_sum[kNbSums];
     const NbState st = a.st[a.level % kNbRing];
     if (st.done || !st.tdm) return;
@@ -328,12 +327,7 @@ __global__ __launch_bounds__(kBlock) void nb_td_kernel(NbLevel a) {
     const int ept = mf <= nthreads ? 1 : kNbEpt;
     const int64_t per_tile = nthreads * ept;
     const int64_t tiles = (mf + per_tile - 1) / per_tile;
-    // samples of the queue's edge offsets
-    const int64_t qstride = (nq + kNbSamples - 1) / kNbSamples > 0 ? (nq + kNbSamples - 1) / kNbSamples : 1;
-    const int64_t qcount = (nq + qstride - 1) / qstride;
-    if ((int64_t)blockIdx.x * blockDim.x * ept < mf)
-        for (int64_t j = threadIdx.x; j < qcount; j += blockDim.x) s_qs[j] = a.qoff_in[j * qstride];
-    __syncthreads();
+    const QoffIndex qi = stage_qoff(a.qoff_in, nq, mf, ept, s_qs);
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x + wave_id() * kWave) * ept >= mf) break;
         const int64_t e0 = (t * nthreads + tid) * ept;
@@ -342,28 +336,15 @@ __global__ __launch_bounds__(kBlock) void nb_td_kernel(NbLevel a) {
 #pragma unroll
         for (int k = 0; k < kNbEpt; ++k) v[k] = 0, bits[k] = 0;
         if (e0 < mf) {
-            int64_t lo = 0, hi = qcount - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (s_qs[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            int64_t g0 = lo * qstride, g1 = (g0 + qstride < nq ? g0 + qstride : nq) - 1;
-            while (g0 < g1) {
-                const int64_t mid = (g0 + g1 + 1) >> 1;
-                if (a.qoff_in[mid] <= e0) g0 = mid; else g1 = mid - 1;
-            }
-            int64_t i = g0;
-            int64_t next_bound = i + 1 < nq ? a.qoff_in[i + 1] : mf;
+            EdgeCursor cur{a.qoff_in, nq, mf};
+            cur.seek_entry(find_entry(a.qoff_in, qi, nq, e0));
 #pragma unroll
             for (int k = 0; k < kNbEpt; ++k) {
                 const int64_t e = e0 + k;
                 if (k < ept && e < mf) {
-                    while (e >= next_bound) {  // zero-degree queue rows too
-                        ++i;
-                        next_bound = i + 1 < nq ? a.qoff_in[i + 1] : mf;
-                    }
-                    const int32_t u = a.queue_in[i];
-                    v[k] = a.push_col[a.push_rp[u] + (e - a.qoff_in[i])];
+                    cur.advance(e);
+                    const int32_t u = a.queue_in[cur.i];
+                    v[k] = a.push_col[a.push_rp[u] + cur.row_offset(e)];
                     bits[k] = a.Fc[u] & tdm;
                     sum.ex += 1;
                 }
@@ -510,9 +491,7 @@ NarrowRun narrow_bfs(Ctx& ctx, Shard& sh, const Csr& push, const Csr& pull, cons
     NbCtr* ctr = reinterpret_cast<NbCtr*>(sh.nb_ctr.get());
     NbState* st = reinterpret_cast<NbState*>(sh.nb_state.get());
 
-    hipEvent_t t0, t1;
-    JG_HIP(hipEventCreate(&t0));
-    JG_HIP(hipEventCreate(&t1));
+    Event t0, t1;
     JG_HIP(hipEventRecord(t0, s));
     if (prof_enabled(ctx)) prof_record_start(ctx, sh);
     JG_HIP(hipMemsetAsync(sh.nb_vis.get(), 0, (size_t)rows, s));
@@ -587,8 +566,6 @@ NarrowRun narrow_bfs(Ctx& ctx, Shard& sh, const Csr& push, const Csr& pull, cons
     JG_HIP(hipEventSynchronize(t1));
     NarrowRun out;
     JG_HIP(hipEventElapsedTime(&out.ms, t0, t1));
-    JG_HIP(hipEventDestroy(t0));
-    JG_HIP(hipEventDestroy(t1));
     out.levels = hs.levels;
     // work: the examined entries of every level and the reached (source, row) pairs; the sources'
     // own pairs (level 0) are not counted by the kernels

@@ -155,40 +155,6 @@ __device__ BfsState bfs_decide(const BfsLevel& a, int64_t* nf_out, int64_t* mf_o
 // (RMAT-20 level 1: 329 K entries, 107 K targets, 64 us); plain stores to one address do not.
 enum TdMode { kTdCas = 0, kTdOwner = 1, kTdClaim = 2 };
 
-// Queue-entry search of the edge-parallel top-down: every stride-th edge offset of the input queue
-// (stride = ceil(nf / kQoffSamples)) is staged in LDS by each block with work, the
-// search runs there and then over at most `qs` global offsets.  The offsets were appended by every XCD
-// in the previous launch, so each global probe misses the reading XCD's L2: a 22.6 K-entry queue cost
-// 15 dependent probes (RMAT-20 level 4, a 24.9 K-entry top-down level: 12.4 us).
-constexpr int kQoffSamples = 1024;
-struct QoffIndex {
-    const int64_t* lds;  // samples: lds[j] = qoff_in[j * stride]
-    int64_t stride, count;
-};
-__device__ __forceinline__ QoffIndex stage_qoff(const BfsLevel& a, int64_t nf, int64_t mf, int ept, int64_t* s_qs) {
-    QoffIndex q{s_qs, (nf + kQoffSamples - 1) / kQoffSamples, 0};
-    q.count = (nf + q.stride - 1) / q.stride;
-    if ((int64_t)blockIdx.x * blockDim.x * ept < mf)  // block-uniform: blocks past the frontier's edges skip it
-        for (int64_t j = threadIdx.x; j < q.count; j += blockDim.x) s_qs[j] = a.qoff_in[j * q.stride];
-    __syncthreads();
-    return q;
-}
-// the queue entry i with qoff_in[i] <= e < qoff_in[i + 1] (offsets are monotone; zero-degree entries
-// share their successor's offset and the search returns the last of them)
-__device__ __forceinline__ int64_t find_entry(const BfsLevel& a, const QoffIndex& q, int64_t nf, int64_t e) {
-    int64_t lo = 0, hi = q.count - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) >> 1;
-        if (q.lds[mid] <= e) lo = mid; else hi = mid - 1;
-    }
-    int64_t g0 = lo * q.stride, g1 = std::min(g0 + q.stride, nf) - 1;
-    while (g0 < g1) {
-        const int64_t mid = (g0 + g1 + 1) >> 1;
-        if (a.qoff_in[mid] <= e) g0 = mid; else g1 = mid - 1;
-    }
-    return g0;
-}
-
 template <int kMode, class App>
 __device__ __forceinline__ void bfs_top_down(const BfsLevel& a, int64_t nf, int64_t mf, unsigned long long* packed,
                                              App& app, int64_t* s_qs) {
@@ -198,7 +164,7 @@ __device__ __forceinline__ void bfs_top_down(const BfsLevel& a, int64_t nf, int6
     const int64_t per_tile = nthreads * ept;
     const int64_t tiles = (mf + per_tile - 1) / per_tile;  // wave-uniform
     const int32_t next_depth = a.level + 1;
-    const QoffIndex qi = stage_qoff(a, nf, mf, ept, s_qs);
+    const QoffIndex qi = stage_qoff(a.qoff_in, nf, mf, ept, s_qs);
     for (int64_t t = 0; t < tiles; ++t) {
         // a block (a wave, with wave-staged appends) whose slice of this tile is past the frontier's
         // edges has nothing to claim or append (small frontiers leave most of the grid idle)
@@ -209,20 +175,17 @@ __device__ __forceinline__ void bfs_top_down(const BfsLevel& a, int64_t nf, int6
         bool have[kTdEdgesPerThread], won[kTdEdgesPerThread];
         int64_t vdeg[kTdEdgesPerThread];
         if (e0 < mf) {
-            int64_t i = find_entry(a, qi, nf, e0);
-            int64_t next_bound = i + 1 < nf ? a.qoff_in[i + 1] : mf;
+            EdgeCursor cur{a.qoff_in, nf, mf};
+            cur.seek_entry(find_entry(a.qoff_in, qi, nf, e0));
 #pragma unroll
             for (int k = 0; k < kTdEdgesPerThread; ++k) {
                 const int64_t e = e0 + k;
                 have[k] = k < ept && e < mf;
                 v[k] = 0;
                 if (have[k]) {
-                    while (e >= next_bound) {  // skips zero-degree frontier entries too
-                        ++i;
-                        next_bound = i + 1 < nf ? a.qoff_in[i + 1] : mf;
-                    }
-                    const int32_t u = a.queue_in[i];
-                    v[k] = a.push_col[a.push_rp[u] + (e - a.qoff_in[i])];
+                    cur.advance(e);
+                    const int32_t u = a.queue_in[cur.i];
+                    v[k] = a.push_col[a.push_rp[u] + cur.row_offset(e)];
                 }
             }
         } else {
@@ -957,28 +920,17 @@ __global__ __launch_bounds__(kBlock) void msbfs_td_kernel(MsTd a) {
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x) * kTdEdgesPerThread >= a.mf) break;  // block-uniform
         const int64_t e0 = (t * nthreads + tid) * kTdEdgesPerThread;
-        int64_t i = 0, next_bound = 0;
-        if (e0 < a.mf) {
-            int64_t lo = 0, hi = a.nq - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (a.qoff[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            i = lo;
-            next_bound = i + 1 < a.nq ? a.qoff[i + 1] : a.mf;
-        }
+        EdgeCursor cur{a.qoff, a.nq, a.mf};
+        if (e0 < a.mf) cur.seek(e0);
 #pragma unroll
         for (int k = 0; k < kTdEdgesPerThread; ++k) {
             const int64_t e = e0 + k;
             bool take = false, hfirst = false;
             int32_t u = 0;
             if (e < a.mf) {
-                while (e >= next_bound) {
-                    ++i;
-                    next_bound = i + 1 < a.nq ? a.qoff[i + 1] : a.mf;
-                }
-                const int32_t v = a.queue[i];
-                u = a.push_col[a.push_rp[v] + (e - a.qoff[i])];
+                cur.advance(e);
+                const int32_t v = a.queue[cur.i];
+                u = a.push_col[a.push_rp[v] + cur.row_offset(e)];
                 const unsigned long long fv = a.F[v];
                 if ((u >> a.tbits) == 0) {
                     const unsigned long long w = fv & ~(a.probe_visited ? a.visited[u] : 0ull);
@@ -1366,28 +1318,17 @@ __global__ __launch_bounds__(kBlock) void sd_push_q_kernel(SdPush a) {
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x) * kTdEdgesPerThread >= mf) break;  // block-uniform
         const int64_t e0 = (t * nthreads + tid) * kTdEdgesPerThread;
-        int64_t i = 0, next_bound = 0;
-        if (e0 < mf) {
-            int64_t lo = 0, hi = nq - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (qoff[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            i = lo;
-            next_bound = i + 1 < nq ? qoff[i + 1] : mf;
-        }
+        EdgeCursor cur{qoff, nq, mf};
+        if (e0 < mf) cur.seek(e0);
 #pragma unroll
         for (int k = 0; k < kTdEdgesPerThread; ++k) {
             const int64_t e = e0 + k;
             bool first = false;
             int32_t u = 0;
             if (e < mf) {
-                while (e >= next_bound) {
-                    ++i;
-                    next_bound = i + 1 < nq ? qoff[i + 1] : mf;
-                }
-                const int32_t w = frontier[i];
-                const int64_t j = a.rp[w] + (e - qoff[i]);
+                cur.advance(e);
+                const int32_t w = frontier[cur.i];
+                const int64_t j = a.rp[w] + cur.row_offset(e);
                 u = a.col[j];
                 const int32_t wk = a.wt ? a.wt[j] : 1;
                 if (wk == kWeightAbsent) {  // the edge function would throw (ShortestDistanceVertexProgram.java:69)
@@ -1620,16 +1561,8 @@ __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x) * kTdEdgesPerThread >= mf) break;  // block-uniform
         const int64_t e0 = (t * nthreads + tid) * kTdEdgesPerThread;
-        int64_t i = 0, next_bound = 0;
-        if (e0 < mf) {
-            int64_t lo = 0, hi = nq - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (qoff[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            i = lo;
-            next_bound = i + 1 < nq ? qoff[i + 1] : mf;
-        }
+        EdgeCursor cur{qoff, nq, mf};
+        if (e0 < mf) cur.seek(e0);
 #pragma unroll
         for (int k = 0; k < kTdEdgesPerThread; ++k) {
             const int64_t e = e0 + k;
@@ -1637,12 +1570,9 @@ __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
             int32_t u = 0;
             int64_t du = 0;
             if (e < mf) {
-                while (e >= next_bound) {
-                    ++i;
-                    next_bound = i + 1 < nq ? qoff[i + 1] : mf;
-                }
-                const int32_t w = near[i];
-                const int64_t j = a.rp[w] + (e - qoff[i]);
+                cur.advance(e);
+                const int32_t w = near[cur.i];
+                const int64_t j = a.rp[w] + cur.row_offset(e);
                 u = a.col[j];
                 const int32_t wk = a.wt ? a.wt[j] : 1;
                 if (wk == kWeightAbsent) {  // the edge function would throw (ShortestDistanceVertexProgram.java:69)
@@ -1777,28 +1707,17 @@ __global__ __launch_bounds__(kBlock) void ssd_push_q_kernel(SsdPushQ a) {
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x) * kTdEdgesPerThread >= a.mf) break;  // block-uniform
         const int64_t e0 = (t * nthreads + tid) * kTdEdgesPerThread;
-        int64_t i = 0, next_bound = 0;
-        if (e0 < a.mf) {
-            int64_t lo = 0, hi = a.nq - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (a.qoff[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            i = lo;
-            next_bound = i + 1 < a.nq ? a.qoff[i + 1] : a.mf;
-        }
+        EdgeCursor cur{a.qoff, a.nq, a.mf};
+        if (e0 < a.mf) cur.seek(e0);
 #pragma unroll
         for (int k = 0; k < kTdEdgesPerThread; ++k) {
             const int64_t e = e0 + k;
             bool first = false;
             int32_t u = 0;
             if (e < a.mf) {
-                while (e >= next_bound) {
-                    ++i;
-                    next_bound = i + 1 < a.nq ? a.qoff[i + 1] : a.mf;
-                }
-                const int32_t w = a.frontier[i];
-                const int64_t j = a.rp[w] + (e - a.qoff[i]);
+                cur.advance(e);
+                const int32_t w = a.frontier[cur.i];
+                const int64_t j = a.rp[w] + cur.row_offset(e);
                 u = a.col[j];
                 const int32_t wk = a.wt ? a.wt[j] : 1;
                 if (wk == kWeightAbsent) {
@@ -2297,16 +2216,8 @@ __device__ __forceinline__ void sbfs_td_push(const SBfsLevel& a, int64_t nq, int
     for (int64_t t = 0; t < tiles; ++t) {
         if ((t * nthreads + bid * blockDim.x + wave_id() * kWave) * kTdEdgesPerThread >= mf) break;  // wave-uniform
         const int64_t e0 = (t * nthreads + tid) * kTdEdgesPerThread;
-        int64_t i = 0, next_bound = 0;
-        if (e0 < mf) {
-            int64_t lo = 0, hi = nq - 1;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi + 1) >> 1;
-                if (a.qoff_in[mid] <= e0) lo = mid; else hi = mid - 1;
-            }
-            i = lo;
-            next_bound = i + 1 < nq ? a.qoff_in[i + 1] : mf;
-        }
+        EdgeCursor cur{a.qoff_in, nq, mf};
+        if (e0 < mf) cur.seek(e0);
 #pragma unroll
         for (int k = 0; k < kTdEdgesPerThread; ++k) {
             const int64_t e = e0 + k;
@@ -2314,12 +2225,9 @@ __device__ __forceinline__ void sbfs_td_push(const SBfsLevel& a, int64_t nq, int
             int32_t u = 0;
             int64_t deg = 0;
             if (e < mf) {
-                while (e >= next_bound) {
-                    ++i;
-                    next_bound = i + 1 < nq ? a.qoff_in[i + 1] : mf;
-                }
-                const int32_t v = a.queue_in[i];
-                u = a.col[a.rp[v] + (e - a.qoff_in[i])];
+                cur.advance(e);
+                const int32_t v = a.queue_in[cur.i];
+                u = a.col[a.rp[v] + cur.row_offset(e)];
                 if (u < a.rows) {
                     if (!a.seen[u] && atomicCAS(&a.dvec[u], -1, nd) == -1) {
                         a.seen[u] = 1;
@@ -2908,11 +2816,9 @@ int dobfs_sharded(Graph& g, int64_t src_shard, int64_t src_local, int max_depth,
                                           1);
         gpost[i] = dim3((unsigned)std::max(fx, st[i].apply_x), (unsigned)g.P);
     }
-    hipEvent_t t0, t1;
+    Event t0(sh0.device), t1(sh0.device);
     {
         DeviceGuard dg(sh0.device);
-        JG_HIP(hipEventCreate(&t0));
-        JG_HIP(hipEventCreate(&t1));
         for (auto& sp : g.shards) {
             DeviceGuard dgs(*sp);
             JG_HIP(hipStreamSynchronize(sp->stream));  // the plan copies above; t0 marks the traversal's start
@@ -3000,8 +2906,6 @@ int dobfs_sharded(Graph& g, int64_t src_shard, int64_t src_local, int max_depth,
         region_mark(sh0.stream, false);
         JG_HIP(hipEventSynchronize(t1));
         JG_HIP(hipEventElapsedTime(ms_out, t0, t1));
-        JG_HIP(hipEventDestroy(t0));
-        JG_HIP(hipEventDestroy(t1));
     }
     for (size_t i = 0; i < ns; ++i) {
         Shard& sh = *g.shards[i];
@@ -3130,11 +3034,9 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
     const bool single = nsrc == 1 && g.P == 1;
     const bool sharded_do = nsrc == 1 && g.P > 1 && g.P <= kMaxShardsBfs && direction == JG_DIR_BOTH &&
                             g.shards[0]->halo_both.on && tune().sharded_bfs;
-    hipEvent_t t0, t1;
     Shard& sh0 = *g.shards[0];
     DeviceGuard dg0(sh0.device);
-    JG_HIP(hipEventCreate(&t0));
-    JG_HIP(hipEventCreate(&t1));
+    Event t0, t1;
     if (sharded_do) {
         int shard = -1;
         const int64_t l = local_of_vid(g, source_vids[0], &shard);
@@ -3759,7 +3661,7 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
                                 }
                             }
                             sparse_done = true;
-                            if (std::getenv("JG_DEBUG_BFS"))
+                            if (debug_bfs())
                                 std::fprintf(stderr, "[jg msbfs] level %d top-down, sparse reverse exchange: %lld pairs (dense: %lld words)\n",
                                              level, (long long)pairs_all, (long long)mat[(size_t)P * P]);
                         }
@@ -4083,8 +3985,6 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
         ctx.last.edges_traversed = work_entries;  // adjacency entries the levels examined
         prof_collect(ctx, g);
     }
-    JG_HIP(hipEventDestroy(t0));
-    JG_HIP(hipEventDestroy(t1));
 }
 
 // Sharded ShortestDistanceVertexProgram (weighted or unit): the same exact supersteps as the single
@@ -4154,11 +4054,9 @@ static void shortest_distance_sharded(Graph& g, int64_t seed_vid, int max_depth,
     int64_t total = seed_local >= 0 ? 1 : 0;
     allreduce_sum_i64(g, &total, 1);
     Shard& sh0 = *g.shards[0];
-    hipEvent_t t0, t1;
+    Event t0(sh0.device), t1(sh0.device);
     {
         DeviceGuard dg(sh0.device);
-        JG_HIP(hipEventCreate(&t0));
-        JG_HIP(hipEventCreate(&t1));
         region_mark(sh0.stream, true);
         JG_HIP(hipEventRecord(t0, sh0.stream));
     }
@@ -4242,8 +4140,6 @@ static void shortest_distance_sharded(Graph& g, int64_t seed_vid, int max_depth,
         region_mark(sh0.stream, false);
         JG_HIP(hipEventSynchronize(t1));
         JG_HIP(hipEventElapsedTime(&ms, t0, t1));
-        (void)hipEventDestroy(t0);
-        (void)hipEventDestroy(t1);
     }
     int missing = 0;
     for (size_t i = 0; i < ns; ++i) {
@@ -4396,9 +4292,7 @@ void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* d
     int shard = 0;
     const int64_t seed = local_of_vid(g, seed_vid, &shard);
     std::vector<int64_t> host(rows, LLONG_MIN);  // absent
-    hipEvent_t t0, t1;
-    JG_HIP(hipEventCreate(&t0));
-    JG_HIP(hipEventCreate(&t1));
+    Event t0, t1;
     if (seed >= 0 && !g.has_weights) {
         bfs_buffers(sh);
         if (sh.out.present()) bfs_first_col(sh, sh.out);  // the traversal's pull adjacency
@@ -4488,8 +4382,6 @@ void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* d
     JG_HIP(hipEventSynchronize(t1));
     float ms = 0;
     JG_HIP(hipEventElapsedTime(&ms, t0, t1));
-    JG_HIP(hipEventDestroy(t0));
-    JG_HIP(hipEventDestroy(t1));
     ctx.last.compute_ms = ms;
     ctx.last.levels = levels;
     ctx.last.supersteps = max_depth;  // Fulgora always runs supersteps 0..maxDepth

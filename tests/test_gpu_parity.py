@@ -659,3 +659,39 @@ def test_bfs_tail_grid_deeper_than_history(oracle_lib, tail):
         c.close()
     finally:
         _lib.tune_set("bfs_tail_grid", 64)
+
+
+def test_edge_walk_crosses_tiles(oracle_lib):
+    """The frontier edge walk (EdgeCursor, jg_frontier.h) over more than one tile.  At the default grids
+    the small parity graphs fit every top-down level into one tile, so a thread only ever looks up its
+    first edge; with bfs_grid at its minimum (64 workgroups: a tile is 64 x 256 x 4 = 65,536 entries) a
+    larger level makes every thread search a second time, in a later tile.  One RMAT-16 graph against the
+    oracle: a single-source BFS over BOTH and over OUT (the OUT push has zero-degree queue entries), 8
+    sources (the narrow engine) and 64 sources (the bit-parallel engine).  The alpha thresholds at 1 keep
+    the big levels top-down (at their defaults the levels past ~70 K entries run bottom-up).
+    Observed top-down levels (JG_DEBUG_BFS, this graph and these sources): BOTH level 1 278,221 entries;
+    OUT level 1 67,955; narrow level 1 180,798 (all 8 sources top-down); 64 sources levels 1-4 905,811 /
+    2,085,999 / 2,071,023 / 161,802.  At the default thresholds none of them runs a level past 65,536."""
+    import janusgraph_amd as jg
+    from janusgraph_amd import _lib
+    n, vid, src, dst, ds, dd = rmat_case(oracle_lib, 16)
+    sv = int(ds[5])
+    srcs = np.unique(ds)[::97][:64]
+    want = {(int(s), d): oracle_lib.bfs(n, ds, dd, int(s), d) for d, ss in ((3, srcs), (1, [sv]), (3, [sv])) for s in ss}
+    try:
+        _lib.tune_set("bfs_grid", 64)
+        for k in ("dobfs_alpha", "bfs_alpha", "nb_alpha"):
+            _lib.tune_set(k, 1)
+        c = jg.Context((0,))
+        for flags, cases in ((4, (([sv], 3), (srcs[:8], 3), (srcs, 3))), (3, (([sv], 1),))):
+            g = c.build(vid, src, dst, flags=flags)
+            for sources, d in cases:
+                got = g.bfs(vid[np.asarray(sources)], d)
+                for k, s in enumerate(sources):
+                    np.testing.assert_array_equal(got[k], want[(int(s), d)],
+                                                  err_msg=f"{len(sources)} sources, direction {d}, source {k}")
+            g.close()
+        c.close()
+    finally:
+        for k, v in (("bfs_grid", 8192), ("dobfs_alpha", 30), ("bfs_alpha", 14), ("nb_alpha", 30)):
+            _lib.tune_set(k, v)
