@@ -21,6 +21,10 @@
  *   jg_graph_build_edgestore
  *       the same, from the raw rows: the row decode of VertexJobConverter.process and
  *       EdgeSerializer.parseRelation (graphdb/database/EdgeSerializer.java:86-122) on the GPU
+ *   jg_builder_keep_labels / jg_builder_finish_labels
+ *       the typed vertex-centric queries of a MessageScope.Local such as __.inE("battled")
+ *       (graphdb/olap/computer/VertexProgramScanJob.java:126-134,
+ *       graphdb/query/vertex/BasicVertexCentricQueryBuilder.java:482-587)
  *   jg_pagerank (+ begin/step/end)
  *       executeVertexProgram superstep loop (FulgoraGraphComputer.java:210-230) running
  *       janusgraph-backend-testutils/.../olap/PageRankVertexProgram.java:89-110, with the gather of
@@ -60,7 +64,9 @@ extern "C" {
 
 /* 2: jg_graph_info.exchange_values appended; jg_bfs_rows, jg_graph_neighbors added.
  * 3: jg_bfs_keep, jg_bfs_kept_row, jg_bfs_kept_release, jg_ctx_trim added.  Callers must check
- * jg_abi_version() == JG_ABI_VERSION before passing any struct across the ABI. */
+ * jg_abi_version() == JG_ABI_VERSION before passing any struct across the ABI.
+ * Still 3 (entry points only, no layout change): jg_builder_keep_labels, jg_builder_add_labeled_edges,
+ * jg_builder_finish_labels added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -259,6 +265,42 @@ int jg_builder_set_query_limit(jg_builder* b, int64_t limit, int32_t in_entries)
 int jg_builder_set_weight_key(jg_builder* b, int64_t weight_key, const int64_t* key_ids, const int8_t* key_types,
                               int32_t nkeys);
 int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out);
+/* ---- label-scoped graphs (typed message scopes) ----
+ * Fulgora turns each MessageScope.Local of a program into a vertex-centric query
+ * (graphdb/olap/computer/VertexProgramScanJob.java:126-134); a scope written __.inE("battled") becomes a
+ * typed query with one slice per label (graphdb/query/vertex/BasicVertexCentricQueryBuilder.java:482-587).
+ * Those slices are fitted, so the 100000-entry cap of graphdb/olap/QueryContainer.java:133 never applies to
+ * them.  Here one snapshot yields any number of label-scoped graphs: the builder keeps a label beside
+ * every edge, and jg_builder_finish_labels cuts a scope out of the accumulated edge list on the GPU.
+ *
+ * jg_builder_keep_labels: must precede every chunk (a builder that holds a chunk or is finished:
+ * JG_ERR_STATE).  Mutually exclusive with a positive jg_builder_set_query_limit, in either order: the
+ * second of the two returns JG_ERR_STATE (typed scopes are fitted, never capped).
+ *   Rows (jg_builder_add_rows, unchanged otherwise): the label of a kept edge is its relation type id, the
+ *   value jg_decode_edges returns in type_out.
+ *   Ids: every edge chunk arrives through jg_builder_add_labeled_edges, label[m] opaque int64 values (weights
+ *   on every chunk or none, as jg_builder_add_edges); plain jg_builder_add_edges on a label-keeping builder
+ *   returns JG_ERR_ARG, jg_builder_add_labeled_edges without jg_builder_keep_labels JG_ERR_STATE.
+ *
+ * jg_builder_finish_labels: the graph of ALL vertices added (V is never filtered) and of the edges whose
+ * label is in labels[0, nlabels).  Duplicates in labels are ignored; a label no edge carries matches
+ * nothing (BasicVertexCentricQueryBuilder.java:484 skips unknown types) and legally gives zero edges.
+ * nlabels < 1, null labels or more than JG_MAX_SCOPE_LABELS distinct labels: JG_ERR_ARG; without
+ * jg_builder_keep_labels: JG_ERR_STATE.  The call completes the pending chunks and seals the builder (later
+ * add_* calls: JG_ERR_STATE) but does not finish it: it may be called any number of times, and a final
+ * jg_builder_finish is still allowed (it covers every label, then finishes the builder as always).  Every
+ * graph of one builder reports the same jg_graph_vertex_ids and survives jg_builder_destroy.  The
+ * jg_graph_info counts (num_edges, ghost_edges, self_loops, max degrees) describe the scope only, and the
+ * 2^32-1 edge limit applies to the scope, not to the accumulated list.  flags, logical shards and rank mode
+ * behave as in jg_builder_finish.  Stats: build_ms (the whole call), kernel_ms_total = HIP-event time of
+ * the scope select, kernel_launches = the select's own launches (the count, then the scatter if anything is
+ * kept; 0 for an empty edge list), algorithmic_bytes = 16 B per accumulated edge (its label read twice) +
+ * 2 x 16 B (20 B with weights) per kept edge (read, then written). */
+#define JG_MAX_SCOPE_LABELS 1024
+int jg_builder_keep_labels(jg_builder* b);
+int jg_builder_add_labeled_edges(jg_builder* b, const int64_t* src, const int64_t* dst, const int32_t* weight,
+                                 const int64_t* label, int64_t m);
+int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabels, uint32_t flags, jg_graph** out);
 int jg_builder_destroy(jg_builder* b);
 /* vid_out[i] = the id of vertex offset + i in output order (the order vid[] / the kept rows were given). */
 int jg_graph_vertex_ids(const jg_graph* g, int64_t offset, int64_t count, int64_t* vid_out);

@@ -43,10 +43,13 @@ EXPORTS = [
     "jg_builder_add_rows", "jg_builder_finish", "jg_builder_destroy", "jg_graph_vertex_ids",
     "jg_builder_set_query_limit", "jg_bfs_rows", "jg_graph_neighbors", "jg_builder_set_weight_key",
     "jg_bfs_keep", "jg_bfs_kept_row", "jg_bfs_kept_release", "jg_ctx_trim",
+    "jg_builder_keep_labels", "jg_builder_add_labeled_edges", "jg_builder_finish_labels",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
     PROP_STRING = range(1, 12)
+MAX_SCOPE_LABELS = 1024  # JG_MAX_SCOPE_LABELS: distinct labels of one jg_builder_finish_labels scope
+SCOPE_TILE = 2048  # edges per tile of the scope select (kScopeTile, csrc/jg_internal.h)
 ABI_VERSION = 3  # JG_ABI_VERSION of include/janusgpu.h this binding's structs follow
 
 
@@ -190,6 +193,9 @@ def load():
         "jg_bfs_kept_row": ([_P, _i32, _P], ctypes.c_int),
         "jg_bfs_kept_release": ([_P], ctypes.c_int),
         "jg_ctx_trim": ([_P], ctypes.c_int),
+        "jg_builder_keep_labels": ([_P], ctypes.c_int),
+        "jg_builder_add_labeled_edges": ([_P, _P, _P, _P, _P, _i64], ctypes.c_int),
+        "jg_builder_finish_labels": ([_P, _P, _i32, ctypes.c_uint32, _PP], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -357,7 +363,9 @@ class Context:
 
 
 class Builder:
-    """jg_builder_*: add_vertices / add_edges chunks, or set_schema then add_rows chunks, then finish()."""
+    """jg_builder_*: add_vertices / add_edges chunks, or set_schema then add_rows chunks, then finish().
+    After keep_labels() every edge carries a label (ids: add_edges(..., label=...); rows: the relation type
+    id) and finish_labels(labels) builds the graph of one label scope, any number of times."""
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
@@ -382,7 +390,13 @@ class Builder:
         vid = np.ascontiguousarray(vid, np.int64)
         check(load().jg_builder_add_vertices(self._h, _ptr(vid), len(vid)))
 
-    def add_edges(self, src, dst, weight=None):
+    def keep_labels(self):
+        """jg_builder_keep_labels: keep a label beside every edge (before the first chunk; not under a
+        positive query limit)."""
+        check(load().jg_builder_keep_labels(self._h))
+
+    def add_edges(self, src, dst, weight=None, label=None):
+        """jg_builder_add_edges, or with `label` (one int64 per edge) jg_builder_add_labeled_edges."""
         src = np.ascontiguousarray(src, np.int64)
         dst = np.ascontiguousarray(dst, np.int64)
         if len(src) != len(dst):
@@ -390,7 +404,13 @@ class Builder:
         w = None if weight is None else np.ascontiguousarray(weight, np.int32)
         if w is not None and len(w) != len(src):
             raise ValueError("weight must have one entry per edge")
-        check(load().jg_builder_add_edges(self._h, _ptr(src), _ptr(dst), _ptr(w), len(src)))
+        if label is None:
+            check(load().jg_builder_add_edges(self._h, _ptr(src), _ptr(dst), _ptr(w), len(src)))
+            return
+        lab = np.ascontiguousarray(label, np.int64)
+        if lab.ndim != 1 or len(lab) != len(src):
+            raise ValueError("label must have one entry per edge")
+        check(load().jg_builder_add_labeled_edges(self._h, _ptr(src), _ptr(dst), _ptr(w), _ptr(lab), len(src)))
 
     def set_schema(self, type_ids=(), type_mult=(), partition_bits=5):
         tid = np.ascontiguousarray(type_ids, np.int64)
@@ -434,6 +454,17 @@ class Builder:
     def finish(self, flags=ADJ_IN | ADJ_OUT | ADJ_BOTH) -> "Graph":
         h = ctypes.c_void_p()
         check(load().jg_builder_finish(self._h, flags, ctypes.byref(h)))
+        g = Graph(self.ctx, h, 0)
+        g.n = g.info()["num_vertices"]
+        return g
+
+    def finish_labels(self, labels, flags=ADJ_IN | ADJ_OUT | ADJ_BOTH) -> "Graph":
+        """jg_builder_finish_labels: the graph of every vertex added and of the edges whose label is in
+        `labels` (at most MAX_SCOPE_LABELS distinct ones; a label no edge carries matches nothing).  Seals
+        the builder against further chunks; may be called again, and finish() afterwards covers all labels."""
+        lab = np.ascontiguousarray(np.atleast_1d(labels), np.int64)
+        h = ctypes.c_void_p()
+        check(load().jg_builder_finish_labels(self._h, _ptr(lab), len(lab), flags, ctypes.byref(h)))
         g = Graph(self.ctx, h, 0)
         g.n = g.info()["num_vertices"]
         return g

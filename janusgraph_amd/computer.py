@@ -237,7 +237,10 @@ class GpuGraphComputer:
             vid, src, dst, _ = g0.snapshot()
             direction = CombinerVertexProgram.SCOPES[vp.scope]
             adj = {_lib.DIR_OUT: _lib.ADJ_OUT, _lib.DIR_IN: _lib.ADJ_IN, _lib.DIR_BOTH: _lib.ADJ_BOTH}[direction]
-            g = ctx.build(vid, src, dst, flags=adj)
+            if vp.labels is None:
+                g = ctx.build(vid, src, dst, flags=adj)
+            else:
+                g = self._label_scoped_graph(ctx, vid, src, dst, vp.labels, adj)
             try:
                 x, received = g.combine_steps(direction, CombinerVertexProgram.COMBINERS.index(vp.combiner), vp.length,
                                               np.full(len(vid), vp.initial_message, np.int64), vp.int32)
@@ -248,6 +251,22 @@ class GpuGraphComputer:
             props = {int(v): {vp.property_key: int(d)} for v, d, k in zip(vid, x, keep) if k}
             return vid, props, vp.length, {}
         raise ProgramNotSupported(type(vp).__name__)
+
+    def _label_scoped_graph(self, ctx, vid, src, dst, labels, flags):
+        """The snapshot through a label-keeping builder, cut down to the typed scope's labels on the GPU
+        (jg_builder_finish_labels).  A name the graph does not know gets an id no edge has: it matches
+        nothing, as BasicVertexCentricQueryBuilder.java:484 skips unknown types."""
+        lab, ids = self.graph.edge_label_ids()
+        unknown = len(ids)
+        scope = [ids.get(name, unknown) for name in labels]
+        b = ctx.builder()
+        try:
+            b.keep_labels()
+            b.add_vertices(vid)
+            b.add_edges(src, dst, label=lab)
+            return b.finish_labels(scope, flags)
+        finally:
+            b.close()
 
     def _shortest_paths(self, ctx, vp):
         """ShortestPaths.execute of the Java drop-in: one depth row per source (jg_bfs_rows, 64 sources

@@ -18,6 +18,7 @@
 
 #include "jg_cache.h"
 #include "jg_internal.h"
+#include "jg_labelset.h"
 
 namespace jg {
 
@@ -598,6 +599,10 @@ struct jg_builder {
     int64_t wkey = -1;
     std::vector<int64_t> wkey_ids;
     std::vector<int8_t> wkey_types;
+    bool keep_labels = false;  // jg_builder_keep_labels: a label beside every edge (ids: lab; rows: dec->lab)
+    bool sealed = false;       // after the first jg_builder_finish_labels: no more chunks
+    jg::DevBuf<int64_t> lab;
+    int64_t ml = 0;
 };
 
 using jg::Error;
@@ -979,6 +984,7 @@ int jg_builder_add_vertices(jg_builder* b, const int64_t* vid, int64_t n) {
     JG_GUARD_BEGIN
     JG_ARG(b && n >= 0 && (n == 0 || vid), "bad arguments");
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
+    if (b->sealed) jg::fail(JG_ERR_STATE, "builder sealed by jg_builder_finish_labels: no more chunks");
     if (b->mode == 2) jg::fail(JG_ERR_STATE, "builder holds edgestore rows: vertices come from the rows");
     b->mode = 1;
     jg::DeviceGuard dg(builder_device(b));
@@ -986,12 +992,21 @@ int jg_builder_add_vertices(jg_builder* b, const int64_t* vid, int64_t n) {
     JG_GUARD_END
 }
 
-int jg_builder_add_edges(jg_builder* b, const int64_t* src, const int64_t* dst, const int32_t* weight, int64_t m) {
-    JG_GUARD_BEGIN
+extern "C++" {
+namespace {
+// jg_builder_add_edges (label null) and jg_builder_add_labeled_edges
+void builder_add_edges(jg_builder* b, const int64_t* src, const int64_t* dst, const int32_t* weight,
+                       const int64_t* label, bool labeled, int64_t m) {
     JG_ARG(b && m >= 0 && (m == 0 || (src && dst)), "bad arguments");
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
+    if (b->sealed) jg::fail(JG_ERR_STATE, "builder sealed by jg_builder_finish_labels: no more chunks");
     if (b->mode == 2) jg::fail(JG_ERR_STATE, "builder holds edgestore rows: edges come from the rows");
-    if (m == 0) return JG_OK;
+    if (labeled && !b->keep_labels)
+        jg::fail(JG_ERR_STATE, "jg_builder_add_labeled_edges needs jg_builder_keep_labels before the first chunk");
+    if (!labeled && b->keep_labels)
+        jg::fail(JG_ERR_ARG, "the builder keeps labels: edges come through jg_builder_add_labeled_edges");
+    JG_ARG(!labeled || m == 0 || label, "label is null");
+    if (m == 0) return;
     const int wmode = weight ? 1 : 0;
     if (b->weights >= 0 && b->weights != wmode) jg::fail(JG_ERR_ARG, "edge weights must be given for every chunk or none");
     b->weights = wmode;
@@ -1002,6 +1017,31 @@ int jg_builder_add_edges(jg_builder* b, const int64_t* src, const int64_t* dst, 
     builder_append(b->src, b->m, src, m, s);
     builder_append(b->dst, m2, dst, m, s);
     if (weight) builder_append(b->w, b->mw, weight, m, s);
+    if (labeled) builder_append(b->lab, b->ml, label, m, s);
+}
+}  // namespace
+}  // extern "C++"
+
+int jg_builder_add_edges(jg_builder* b, const int64_t* src, const int64_t* dst, const int32_t* weight, int64_t m) {
+    JG_GUARD_BEGIN
+    builder_add_edges(b, src, dst, weight, nullptr, false, m);
+    JG_GUARD_END
+}
+
+int jg_builder_add_labeled_edges(jg_builder* b, const int64_t* src, const int64_t* dst, const int32_t* weight,
+                                 const int64_t* label, int64_t m) {
+    JG_GUARD_BEGIN
+    builder_add_edges(b, src, dst, weight, label, true, m);
+    JG_GUARD_END
+}
+
+int jg_builder_keep_labels(jg_builder* b) {
+    JG_GUARD_BEGIN
+    JG_ARG(b, "null builder");
+    if (b->finished || b->sealed || b->mode != 0) jg::fail(JG_ERR_STATE, "jg_builder_keep_labels must precede every chunk");
+    if (b->query_limit > 0)
+        jg::fail(JG_ERR_STATE, "labels cannot be kept under a query limit: typed scopes are fitted queries, never capped");
+    b->keep_labels = true;
     JG_GUARD_END
 }
 
@@ -1025,6 +1065,9 @@ int jg_builder_set_query_limit(jg_builder* b, int64_t limit, int32_t in_entries)
     JG_ARG(in_entries == JG_DIR_IN || in_entries == JG_DIR_OUT, "in_entries must be JG_DIR_IN or JG_DIR_OUT");
     if (b->finished || b->mode == 2) jg::fail(JG_ERR_STATE, "jg_builder_set_query_limit must precede every chunk");
     if (b->mode == 1) jg::fail(JG_ERR_STATE, "a query limit applies to edgestore rows, not to vertex / edge ids");
+    if (limit > 0 && b->keep_labels)
+        jg::fail(JG_ERR_STATE, "a query limit cannot be set on a label-keeping builder: typed scopes are fitted queries, "
+                               "never capped");
     b->query_limit = limit;
     b->in_entries = in_entries;
     JG_GUARD_END
@@ -1051,12 +1094,14 @@ int jg_builder_add_rows(jg_builder* b, const uint64_t* row_keys, int64_t nrows, 
     JG_GUARD_BEGIN
     JG_ARG(b, "null builder");
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
+    if (b->sealed) jg::fail(JG_ERR_STATE, "builder sealed by jg_builder_finish_labels: no more chunks");
     if (b->mode == 1) jg::fail(JG_ERR_STATE, "builder holds vertex / edge ids: rows cannot be mixed in");
     b->mode = 2;
     if (!b->dec) {
         b->dec = std::make_unique<jg::EdgestoreDecoder>(b->type_ids.data(), b->type_mult.data(),
                                                         (int32_t)b->type_ids.size(), b->pbits, builder_device(b));
         b->dec->set_query_limit(b->query_limit);
+        b->dec->set_keep_labels(b->keep_labels);
         if (b->weight_key)
             b->dec->set_weight_key(b->wkey, b->wkey_ids.data(), b->wkey_types.data(), (int32_t)b->wkey_ids.size());
     }
@@ -1122,12 +1167,81 @@ int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
         b->src.reset();
         b->dst.reset();
         b->w.reset();
+        b->lab.reset();
     }
     c.last = jg_stats{};
     c.last.build_ms = ms;
     c.last.kernel_ms_total = decode_ms;
     c.last.exchange_ms = copy_ms;
     c.last.kernel_launches = chunks;
+    *out = gh.release();
+    JG_GUARD_END
+}
+
+int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabels, uint32_t flags, jg_graph** out) {
+    JG_GUARD_BEGIN
+    JG_ARG(b && out, "null argument");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~7u) == 0, "bad adjacency flags");
+    if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
+    if (!b->keep_labels) jg::fail(JG_ERR_STATE, "jg_builder_finish_labels needs jg_builder_keep_labels before the first chunk");
+    static_assert(JG_MAX_SCOPE_LABELS == jg::kScopeMaxLabels, "the header's cap is the select's");
+    std::vector<int64_t> set;
+    switch (jg::label_set_prepare(labels, nlabels, set)) {
+        case jg::kLabelSetBadArg: jg::fail(JG_ERR_ARG, "jg_builder_finish_labels needs at least one label");
+        case jg::kLabelSetTooMany:
+            jg::fail(JG_ERR_ARG, "a label scope holds at most " + std::to_string(JG_MAX_SCOPE_LABELS) + " distinct labels");
+        default: break;
+    }
+    *out = nullptr;
+    b->sealed = true;
+    jg::Ctx& c = *b->ctx;
+    auto gh = std::make_unique<jg_graph>(&c);
+    jg::Graph& g = gh->impl;
+    g.flags = flags;
+    jg::make_shards(c, g);
+    jg::BuildTimer timer(g);
+    const int dev0 = builder_device(b);
+    jg::ScopeSelect sel;
+    {
+        jg::DeviceGuard dg(dev0);
+        // the accumulated snapshot: every vertex, and the edge list the scope is cut out of
+        const int64_t *vid, *src, *dst, *lab;
+        const int32_t* w = nullptr;
+        int64_t n, m;
+        if (b->mode == 2) {
+            jg::EdgestoreDecoder& d = *b->dec;
+            d.finish();
+            if (d.vid.size() == 0) d.vid.alloc(1);
+            vid = d.vid.get();
+            n = d.n;
+            src = d.src.get();
+            dst = d.dst.get();
+            lab = d.lab.get();
+            m = d.m;
+            if (d.weighted == 1 && d.w.size() == 0) d.w.alloc(1);
+            if (d.weighted == 1) w = d.w.get();
+        } else {
+            if (b->vid.size() == 0) b->vid.alloc(1);
+            vid = b->vid.get();
+            n = b->n;
+            src = b->src.get();
+            dst = b->dst.get();
+            lab = b->lab.get();
+            m = b->m;
+            if (b->weights == 1) w = b->w.get();
+        }
+        jg::DevBuf<int64_t> ssrc, sdst;
+        jg::DevBuf<int32_t> sw;
+        hipStream_t s = builder_stream(b);
+        sel = jg::scope_select(lab, src, dst, w, m, set, ssrc, sdst, sw, s);
+        jg::build_from_device_ids(g, dev0, s, vid, n, ssrc.get(), sdst.get(), w ? sw.get() : nullptr, sel.kept);
+    }
+    const float ms = timer.stop();
+    c.last = jg_stats{};
+    c.last.build_ms = ms;
+    c.last.kernel_ms_total = sel.ms;
+    c.last.kernel_launches = sel.launches;
+    c.last.algorithmic_bytes = sel.bytes;
     *out = gh.release();
     JG_GUARD_END
 }

@@ -401,6 +401,7 @@ __global__ __launch_bounds__(kBlock) void edgestore_edges_kernel(EntryView a, co
                                                                   const int64_t* __restrict__ row_vid, int pbits,
                                                                   bool with_in, uint8_t* __restrict__ take,
                                                                   int64_t* __restrict__ src, int64_t* __restrict__ dst,
+                                                                  int64_t* __restrict__ etype,
                                                                   int32_t* __restrict__ err) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kStageWords];
     __shared__ int64_t win_off[kRowWin + 1];
@@ -466,6 +467,7 @@ __global__ __launch_bounds__(kBlock) void edgestore_edges_kernel(EntryView a, co
                     t = 1;
                     src[e] = row_vid[r];
                     dst[e] = other;
+                    if (etype) etype[e] = d.type_id;  // jg_builder_keep_labels (null otherwise: a uniform branch)
                 } else if (with_in && d.dir == 1 && d.visible) {  // the IN entry of edge other -> row
                     t = 2;
                     src[e] = other;
@@ -690,7 +692,7 @@ struct EdgestoreChunk {
     int64_t R = 0, E = 0, nbytes = 0;
     PinnedBuf staging;
     DevBuf<uint8_t> d_bytes, keep, keep_v, take, out_flag, in_flag;
-    DevBuf<int64_t> d_off, d_roff, row_vid, esrc, edst, block_row, pre;
+    DevBuf<int64_t> d_off, d_roff, row_vid, esrc, edst, etype, block_row, pre;
     DevBuf<uint32_t> slice;
     DevBuf<unsigned long long> truncated;
     DevBuf<uint8_t> d_meta8;   // narrow staging: entry lengths then value positions
@@ -946,6 +948,7 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
     fit(c.row_vid, R);
     fit(c.esrc, E);
     fit(c.edst, E);
+    if (keep_labels_) fit(c.etype, E);
     fit(c.block_row, (E + kChunk - 1) / kChunk + 1);
     fit(c.d_keys, R);
     fit(c.d_vpos, E);
@@ -1003,7 +1006,7 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
         JG_LAUNCH_CHECK();
         edgestore_edges_kernel<<<grid_for((E + kEpt - 1) / kEpt, kBlock, 256 * 16), kBlock, 0, s>>>(
             a, c.d_roff.get(), c.block_row.get(), R, E, c.keep.get(), c.row_vid.get(), pbits_, capped, c.take.get(),
-            c.esrc.get(), c.edst.get(), c.err.get());
+            c.esrc.get(), c.edst.get(), keep_labels_ ? c.etype.get() : nullptr, c.err.get());
         JG_LAUNCH_CHECK();
     }
     if (capped) {
@@ -1103,6 +1106,11 @@ void EdgestoreDecoder::complete(int slot) {
             gather_kernel<int32_t><<<grid_for(mk), kBlock, 0, s>>>(c.d_w.get(), idx_.get(), mk, tmpw_.get());
             JG_LAUNCH_CHECK();
             grow_append(w, mw, tmpw_.get(), mk, s);
+        }
+        if (keep_labels_) {  // the labels of the kept edges, aligned with src / dst
+            gather_kernel<int64_t><<<grid_for(mk), kBlock, 0, s>>>(c.etype.get(), idx_.get(), mk, tmp_.get());
+            JG_LAUNCH_CHECK();
+            grow_append(lab, ml, tmp_.get(), mk, s);
         }
     }
     JG_HIP(hipStreamSynchronize(s));

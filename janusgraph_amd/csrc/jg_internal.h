@@ -486,6 +486,12 @@ struct EdgestoreDecoder {
     // jg_builder_set_weight_key: decode every OUT edge's Integer weight from its value on the GPU
     void set_weight_key(int64_t key, const int64_t* ids, const int8_t* types, int32_t n);
     int64_t query_limit() const { return limit_; }
+    // jg_builder_keep_labels (before the first add): lab[0, m) = the relation type id of each kept edge,
+    // aligned with src / dst
+    void set_keep_labels(bool on) { keep_labels_ = on; }
+    bool keep_labels() const { return keep_labels_; }
+    DevBuf<int64_t> lab;
+    int64_t ml = 0;
     DevBuf<int64_t> osrc, isrc, idst;
     int64_t mo = 0, mi = 0, mi2 = 0, truncated_rows = 0;
     int weighted = -1;    // -1 no chunk yet, 0 / 1: the chunks carry no / per-entry weights
@@ -498,6 +504,7 @@ struct EdgestoreDecoder {
     void complete(int slot);
     int pbits_, device_;
     int64_t limit_ = 0;
+    bool keep_labels_ = false;
     int next_ = 0;
     hipStream_t streams_[2] = {nullptr, nullptr};
     std::unique_ptr<EdgestoreChunk> chunks_[2];
@@ -514,6 +521,23 @@ void add_in_chunks(EdgestoreDecoder& dec, const EdgestoreRows& r);
 // One-shot: vid = ids of the kept rows (row order), src/dst = their OUT edges, on `device`.
 void edgestore_snapshot(const EdgestoreRows& r, int device, DevBuf<int64_t>& vid, int64_t& n, DevBuf<int64_t>& src,
                         DevBuf<int64_t>& dst, int64_t& m, float* kernel_ms);
+
+// ---- label scope select (jg_scope.hip) ----
+// Stable stream compaction of (src, dst[, w])[0, m) by membership of lab[i] in `set` (sorted, distinct,
+// at most kScopeMaxLabels: label_set_prepare): the kept edges, in their order, land in osrc / odst / ow
+// (allocated here, at least one element; ow only when w is given).  Everything runs on stream s of the
+// current device; the call returns after the one small read-back of the kept count.
+constexpr int kScopeEpt = 8;                                  // edges per thread
+constexpr int64_t kScopeTile = (int64_t)kScopeEpt * kBlock;  // edges per tile (one block iteration)
+struct ScopeSelect {
+    int64_t kept = 0;
+    float ms = 0;          // HIP-event time of the select (count, scan, scatter)
+    int64_t launches = 0;  // its kernel launches
+    double bytes = 0;      // its byte model: labels twice, the kept payload in and out
+};
+ScopeSelect scope_select(const int64_t* lab, const int64_t* src, const int64_t* dst, const int32_t* w, int64_t m,
+                         const std::vector<int64_t>& set, DevBuf<int64_t>& osrc, DevBuf<int64_t>& odst,
+                         DevBuf<int32_t>& ow, hipStream_t s);
 
 // ---- programs ----
 void pagerank_begin(Graph& g, double damping, int64_t vertex_count);

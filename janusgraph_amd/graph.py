@@ -89,6 +89,15 @@ class InMemoryGraph:
             weight = np.asarray(w, dtype=np.int32)
         return vid, src, dst, weight
 
+    def edge_label_ids(self):
+        """(label id per edge int64[m], {label name: id}): one id per stored edge in snapshot()'s edge
+        order, ids assigned by first appearance (0, 1, ...): the labels a typed scope such as
+        __.inE("battled") selects by (jg_builder_keep_labels / jg_builder_finish_labels)."""
+        ids: dict[str, int] = {}
+        lab = np.fromiter((ids.setdefault(e.label, len(ids)) for e in self.edges), dtype=np.int64,
+                          count=len(self.edges))
+        return lab, ids
+
 
 def load_graph_of_the_gods(graph: InMemoryGraph) -> dict:
     """GraphOfTheGodsFactory.load (janusgraph-core/.../example/GraphOfTheGodsFactory.java:116-151)."""

@@ -186,7 +186,10 @@ class CombinerVertexProgram(VertexProgram):
     sending its x_{t-1}: superstep 0 sends `initial_message`, supersteps 1..length store the combined
     value under `property_key` and send it on while t < length; terminate at iteration >= length.
     `scope` is the send scope's direction: "inE" (DegreeCounter's DEG_MSG, OLAPTest.java:429) reaches
-    the sources of a vertex's in-edges, so a vertex receives from its out-neighbours."""
+    the sources of a vertex's in-edges, so a vertex receives from its out-neighbours.
+    `labels` (a tuple of edge label names, None: every edge) types the scope, the __.inE("a", "b") of
+    MessageScope.Local: only edges of those labels carry messages (one fitted slice per label,
+    BasicVertexCentricQueryBuilder.java:482-587); a name the graph does not know matches nothing."""
 
     preferred_result_graph = ResultGraph.NEW
     preferred_persist = Persist.VERTEX_PROPERTIES
@@ -194,13 +197,20 @@ class CombinerVertexProgram(VertexProgram):
     SCOPES = {"inE": 1, "outE": 2, "bothE": 3}  # -> the receiver's pull direction (DIR_OUT/IN/BOTH)
 
     def __init__(self, length=1, property_key="degree", combiner="sum", scope="inE", initial_message=1,
-                 int32=True):
+                 int32=True, labels=None):
         if length <= 0:
             raise ValueError("length must be positive")  # Preconditions.checkArgument(length>0), :438
         if combiner not in self.COMBINERS or scope not in self.SCOPES:
             raise ValueError("unknown combiner or scope")
         self.length, self.property_key, self.combiner, self.scope = length, property_key, combiner, scope
         self.initial_message, self.int32 = initial_message, int32
+        if labels is not None:
+            if isinstance(labels, str):
+                labels = (labels,)
+            labels = tuple(labels)
+            if not labels or not all(isinstance(x, str) for x in labels):
+                raise ValueError("labels must name at least one edge label")
+        self.labels = labels
         self.compute_keys = (property_key,)
         super().__init__({"length": length})
 

@@ -134,6 +134,29 @@ JNIEXPORT jint JNICALL FN(builderFinish)(JNIEnv* env, jclass c, jlong b, jint fl
     return st;
 }
 
+JNIEXPORT jint JNICALL FN(builderKeepLabels)(JNIEnv* env, jclass c, jlong b) {
+    (void)env; (void)c;
+    return jg_builder_keep_labels((jg_builder*)(intptr_t)b);
+}
+
+JNIEXPORT jint JNICALL FN(builderAddLabeledEdges)(JNIEnv* env, jclass c, jlong b, jobject src, jobject dst,
+                                                  jobject weight, jobject label, jlong m) {
+    (void)c;
+    return jg_builder_add_labeled_edges((jg_builder*)(intptr_t)b, (const int64_t*)buf(env, src),
+                                        (const int64_t*)buf(env, dst), (const int32_t*)buf(env, weight),
+                                        (const int64_t*)buf(env, label), m);
+}
+
+JNIEXPORT jint JNICALL FN(builderFinishLabels)(JNIEnv* env, jclass c, jlong b, jobject labels, jint nlabels,
+                                               jint flags, jlongArray out) {
+    (void)c;
+    jg_graph* g = NULL;
+    int st = jg_builder_finish_labels((jg_builder*)(intptr_t)b, (const int64_t*)buf(env, labels), nlabels,
+                                      (uint32_t)flags, &g);
+    put_handle(env, out, g);
+    return st;
+}
+
 JNIEXPORT jint JNICALL FN(graphDestroy)(JNIEnv* env, jclass c, jlong g) {
     (void)env; (void)c;
     return jg_graph_destroy((jg_graph*)(intptr_t)g);

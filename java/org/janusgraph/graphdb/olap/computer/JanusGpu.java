@@ -68,6 +68,14 @@ final class JanusGpu {
     static native int builderSetQueryLimit(long builder, long limit, int inEntries);
     /** jg_builder_finish; graph handle written to out[0]. */
     static native int builderFinish(long builder, int flags, long[] out);
+    /** jg_builder_keep_labels: a label beside every edge (before the first chunk; never with a query limit). */
+    static native int builderKeepLabels(long builder);
+    /** jg_builder_add_labeled_edges: builderAddEdges plus one int64 label per edge (label-keeping builders). */
+    static native int builderAddLabeledEdges(long builder, ByteBuffer src, ByteBuffer dst, ByteBuffer weight,
+                                             ByteBuffer label, long m);
+    /** jg_builder_finish_labels: the graph of one typed scope (labels: int64 direct buffer of nlabels ids);
+     *  graph handle written to out[0].  May be called again; builderFinish afterwards covers every label. */
+    static native int builderFinishLabels(long builder, ByteBuffer labels, int nlabels, int flags, long[] out);
 
     static native int graphDestroy(long graph);
     /** jg_graph_info_get: vertices, edges, ghost edges, self loops, truncated vertices, max in, max out, bytes. */
