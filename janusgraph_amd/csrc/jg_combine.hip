@@ -59,7 +59,6 @@ struct CombOp {
     __device__ __forceinline__ long long gather(int32_t c) const { return x[c]; }
     __device__ __forceinline__ const long long* vec() const { return x; }
     __device__ __forceinline__ long long shfl_xor(long long v, int o) const { return __shfl_xor(v, o, kWave); }
-    __device__ __forceinline__ long long shfl_up(long long v, int d) const { return __shfl_up(v, d, kWave); }
     __device__ __forceinline__ bool active(int64_t) const { return true; }
     __device__ __forceinline__ void finalize(int64_t row, long long acc) const {
         x_out[pos(row)] = finish<OP>(acc, wrap32);

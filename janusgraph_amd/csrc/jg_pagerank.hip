@@ -35,7 +35,6 @@ struct PrOp {
     __device__ __forceinline__ double gather(int32_t c) const { return x[c]; }
     __device__ __forceinline__ const double* vec() const { return x; }
     __device__ __forceinline__ double shfl_xor(double v, int o) const { return __shfl_xor(v, o, kWave); }
-    __device__ __forceinline__ double shfl_up(double v, int d) const { return __shfl_up(v, d, kWave); }
     __device__ __forceinline__ bool active(int64_t) const { return true; }
     __device__ __forceinline__ void finalize(int64_t row, double s) const {
         // (dampingFactor * newPageRank) + ((1D - dampingFactor) / vertexCount), no contraction

@@ -10,10 +10,12 @@
 //            row, fold, then a width-L xor-shuffle tree; lane 0 finalises the row
 //   class 8  the suffix of rows without entries: finalised with the identity, row_ptr not read
 // Every row is folded in a fixed order that does not depend on timing (bit-reproducible runs).
-// An Op supplies: T, identity(), combine(a,b), gather(col), vec(), shfl_xor(v,o),
-// shfl_up(v,d), active(row) (false: the row is not folded but still finalised with identity()),
-// finalize(row, acc).
+// An Op supplies: T (whole dwords), identity(), combine(a,b), gather(col), vec(), shfl_xor(v,o),
+// active(row) (false: the row is not folded but still finalised with identity()), finalize(row, acc),
+// and optionally kTaskLive (op_task_live).
 #pragma once
+
+#include <type_traits>
 
 #include "jg_internal.h"
 #include "jg_prim.h"
@@ -311,7 +313,9 @@ struct HotSegs {
 // from the LDS image of the sub-slice's lines in the hot entries (segment s = g >> (tbits - gshift),
 // its group j = the rest; hot when j < hg, at LDS line s * hg + j), the rest from global memory at
 // the column restored from loc: line = g << bits | (h ^ the hash bits of the group's first line).
-template <class Op>
+// MSEG = false: the vector is one segment (every one-shard plan).  All of a band's groups are below
+// 2^sb then (g < 2^(31 - gshift)), so seg = 0, j = g and the LDS index of a hot entry is loc itself.
+template <class Op, bool MSEG = true>
 struct SliceGather {
     using T = typename Op::T;
     const Op& op;
@@ -321,9 +325,13 @@ struct SliceGather {
     int bits;
     uint32_t hmask, h;  // 2^bits - 1, the sub-slice
     uint32_t idcell;    // the identity cell just past the staged lines
-    __device__ __forceinline__ bool is_hot(uint32_t loc) const { return ((loc >> 4) & ((1u << sb) - 1u)) < hg; }
+    __device__ __forceinline__ bool is_hot(uint32_t loc) const {
+        if constexpr (!MSEG) return loc < (hg << 4);
+        return ((loc >> 4) & ((1u << sb) - 1u)) < hg;
+    }
     // Cold and invalid lanes read the identity cell: no select, so the read cannot become a branch.
     __device__ __forceinline__ T hot(uint32_t loc, bool valid) const {
+        if constexpr (!MSEG) return lds[valid && loc < (hg << 4) ? loc : idcell];
         const uint32_t g = loc >> 4, j = g & ((1u << sb) - 1u), seg = g >> sb;
         return lds[valid && j < hg ? (((seg * hg + j) << 4) | (loc & 15u)) : idcell];
     }
@@ -350,10 +358,31 @@ __device__ __forceinline__ uint32_t unpack_entry(const uint32_t (&d)[W / 4], int
     return v;
 }
 
+// The value of lane (lane - d) mod 64, dword by dword.
+template <class T>
+__device__ __forceinline__ T lane_up(T v, int lane, int d) {
+    static_assert(sizeof(T) % 4 == 0, "whole dwords");
+    int w[sizeof(T) / 4];
+    __builtin_memcpy(w, &v, sizeof(T));
+    const int addr = ((lane - d) & (kWave - 1)) << 2;
+#pragma unroll
+    for (size_t i = 0; i < sizeof(T) / 4; ++i) w[i] = __builtin_amdgcn_ds_bpermute(addr, w[i]);
+    __builtin_memcpy(&v, w, sizeof(T));
+    return v;
+}
+
 // Bands of fewer than 8 sub-slices (2^bits < 8) share each sub-slice among 8 / 2^bits XCDs.
 // (Non-temporal band loads / partial stores measured no gain at RMAT-24/26 in round 2: 4.12-4.25 vs
 // 4.12 ms.)
-template <class Op, bool LDS, int PW>
+// MSEG: the gathered vector has more than one segment (SliceGather).  An Op whose programs pass
+// MergeArgs::live declares `static constexpr bool kTaskLive = true`; for every other Op the bitmap
+// test is not compiled into the task loop.
+template <class Op, class = void>
+struct op_task_live : std::false_type {};
+template <class Op>
+struct op_task_live<Op, std::void_t<decltype(Op::kTaskLive)>> : std::bool_constant<Op::kTaskLive> {};
+
+template <class Op, bool LDS, int PW, bool MSEG = false>
 __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, Op op, typename Op::T* __restrict__ partial,
                                                                    typename Op::T* __restrict__ carry, HotSegs hs,
                                                                    int temporal) {
@@ -370,9 +399,11 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
     const int gshift = 4 + a.bits;
     const int hg = hs.hs >> gshift;  // hot line groups per segment
     const int nl = hs.nseg * hg;     // LDS lines
-    lds_ptr<T> stg = hotv + (nl * 16 + 1) + wave * a.stage;  // this wave's partial window (after the image)
+    // this wave's partial window (after the image): a.stage slots and one dump slot, stg[a.stage],
+    // where the staged fold's lanes without a segment end store (nobody reads it)
+    lds_ptr<T> stg = hotv + (nl * 16 + 1) + wave * (a.stage + 1);
     // the block's task counter (dynamic assignment), after every wave's window
-    lds_ptr<uint32_t> tctr = (lds_ptr<uint32_t>)(hotv + (nl * 16 + 1) + kMergeWaves * a.stage);
+    lds_ptr<uint32_t> tctr = (lds_ptr<uint32_t>)(hotv + (nl * 16 + 1) + kMergeWaves * (a.stage + 1));
     // Static: block w of an XCD folds sub-slice (w mod per) with the XCD's other W / per blocks of it.
     // Temporal: every block of an XCD sweeps the XCD's per sub-slices in the same order, all W blocks
     // on one sub-slice at a time, so the XCD's L2 holds one sub-slice's part of the vector instead
@@ -429,7 +460,7 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
         }
         __syncthreads();
     }
-    const SliceGather<Op> lg{op,       hotv, (uint32_t)hg, hs.tbits - gshift, a.bits, (1u << a.bits) - 1u, (uint32_t)h,
+    const SliceGather<Op, MSEG> lg{op,       hotv, (uint32_t)hg, hs.tbits - gshift, a.bits, (1u << a.bits) - 1u, (uint32_t)h,
                              (uint32_t)nl * 16u};
     const int64_t base = a.sub_base[h];
     const int64_t ntask = a.sub_base[h + 1] - base;
@@ -458,6 +489,7 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
     // a skipped task (a.live): a scalar load of its bit (waiting on it does not wait for the vector
     // gathers in flight), then the next task
     auto dead = [&](int64_t kk) -> bool {
+        if constexpr (!op_task_live<Op>::value) return false;
         if (a.live == nullptr || kk >= ntask) return false;
         const uint64_t tt = (uint64_t)(base + kk);
         const uint32_t wd = __builtin_amdgcn_readfirstlane(a.live[tt >> 5]);
@@ -527,76 +559,120 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
             hb = ld(a.heads + head_idx(kn));
             mw = ld(a.meta + meta_idx(kn));
         }
-        // head numbers: exclusive wave scan of the per-lane head counts
-        const int cnt = __builtin_popcount(hbc);
-        int incl = cnt;
+        // head numbers without a cross-lane scan: ballot b holds the lanes whose head count (0..8) has
+        // bit b set, so the heads in the lanes below this one are the sum over b of 2^b times the
+        // ballot's bits below it (mbcnt), and the task's heads the same sum of the ballots' popcounts
+        // (on the scalar unit).  (One ballot per entry position u gives the same numbers with 8 ballots
+        // instead of 4.)
+        static_assert(kMergeEpl < 16, "a lane's head count has 4 bits");
+        const uint32_t cnt = (uint32_t)__builtin_popcount(hbc);
+        int hbase = 0;  // head number of this lane's first head
+        int H = 0;
 #pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const int o = __shfl_up(incl, d, kWave);
-            if (lane >= d) incl += o;
+        for (int b = 0; b < 4; ++b) {
+            const uint64_t cb = __ballot((cnt >> b) & 1u);
+            hbase += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u)) << b;
+            H += __builtin_popcountll(cb) << b;
         }
-        const int hbase = incl - cnt;  // head number of this lane's first head
         const bool valid_lane = kMergeEpl * lane < n;
         // A task's partials are consecutive slots: with at most `stage` heads they are collected in the
         // wave's LDS window and written by one coalesced store per 64, instead of up to 10 exec-masked
         // scattered stores per lane (the stores cost ~20% of the merge kernel, round 2).
-        const int H = __builtin_amdgcn_readlane(incl, kWave - 1);
         const bool staged = LDS && H <= a.stage;
+        // The segmented scan across lanes below carries the value only.  Classically it also carries a
+        // flag f, f0(l) = lane l holds a head, and at shift d lane l >= d does
+        //     if (!f(l)) x(l) = combine(x(l - d), x(l));   f(l) |= f(l - d);
+        // By induction over the shifts, before shift d f(l) is the OR of f0 over the d lanes
+        // [l - d + 1, l] cut at lane 0: true for d = 1, and shift d ORs in the window of lane l - d,
+        // [l - 2d + 1, l - d], which gives the 2d lanes before shift 2d (for l < d the window already
+        // reaches lane 0 and stays).  So !f(l) before shift d says: no head lane in (l - d, l], that is
+        // gap(l) >= d, gap(l) = the distance from l down to the nearest head lane at or below it (64
+        // when there is none).  Lane l combines at shift d iff l >= d && gap(l) >= d: min(l, gap) >= d.
+        // gap comes from one ballot: shifted so that lane l's bit is bit 63, its leading zeros.
+        const uint64_t hm = __ballot(hbc != 0u);
+        const uint64_t hml = hm << (kWave - 1 - lane);
+        const int gap = hml ? __builtin_clzll(hml) : kWave;
+        const int reach = min(lane, gap);
+        // the head number of the segment that enters this lane from the left: the scan used to carry
+        // it, but it is always the last head of the lanes below
+        const int in_h = hbase - 1;
         // (Folding band 0 into one accumulator per (row, XCD), read-modified-written round by round, was
         // measured 7-9% slower than these partials: profiles/r06/abfold/.)
         auto store_partial = [&](int64_t j, T val) { partial[j] = val; };
-        auto emit = [&](int hh, T val) {  // segment of head hh
-            if (staged) {
-                stg[hh] = val;
-                return;
+        // Hillis-Steele over the lanes' outgoing values (shifts 1, 2, ..., 32; see `reach` above), then
+        // the value that enters each lane from the left
+        // (lane_up, not __shfl_up: the source lane wraps below lane 0 instead of being clamped, which is
+        // two instructions fewer per shift; a lane below the shift never uses what it read)
+        auto scan_in = [&](T x) -> T {
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) {
+                const T xu = lane_up(x, lane, d);
+                if (reach >= d) x = op.combine(xu, x);
             }
-            if (hh == 0 && carry_in) carry[t] = val;
-            else store_partial(j0 + hh, val);
+            return lane_up(x, lane, 1);
         };
-        // lane-local: the part before the first head (continues the segment on the left), inner
-        // segments (emitted here) and the segment of the last head (continues to the right)
-        const int fh = hbc ? __builtin_ctz(hbc) : kMergeEpl;
-        T pre = op.identity(), run = op.identity();
-        int run_h = hbase - 1;
+        // `staged` is decided once per task and each body is compiled for one store path only.
+        // Both fold lane-locally the part before the first head (it continues the segment on the left),
+        // the inner segments (stored at once) and the segment of the last head (it continues to the
+        // right), in entry order, and then combine the lanes by scan_in: the same sums in the same order.
+        auto fold_direct = [&]() {
+            auto emit = [&](int hh, T val) {  // segment of head hh
+                if (hh == 0 && carry_in) carry[t] = val;
+                else store_partial(j0 + hh, val);
+            };
+            const int fh = hbc ? __builtin_ctz(hbc) : kMergeEpl;
+            T pre = op.identity(), run = op.identity();
+            int run_h = hbase - 1;
 #pragma unroll
-        for (int u = 0; u < kMergeEpl; ++u) {
-            if (u < fh) {
-                pre = u == 0 ? v[u] : op.combine(pre, v[u]);
-            } else if ((hbc >> u) & 1u) {
-                if (u > fh) emit(run_h, run);  // the previous head's segment ends here
-                run = v[u];
-                ++run_h;
-            } else {
-                run = op.combine(run, v[u]);
-            }
-        }
-        // segmented inclusive scan across lanes of (lane_out, has_head, head number)
-        T x = fh < kMergeEpl ? run : pre;
-        int f = fh < kMergeEpl ? 1 : 0;
-        int xh = run_h;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const T xu = op.shfl_up(x, d);
-            const int fu = __shfl_up(f, d, kWave);
-            const int hu = __shfl_up(xh, d, kWave);
-            if (lane >= d) {
-                if (!f) {
-                    x = op.combine(xu, x);
-                    xh = hu;
+            for (int u = 0; u < kMergeEpl; ++u) {
+                if (u < fh) {
+                    pre = u == 0 ? v[u] : op.combine(pre, v[u]);
+                } else if ((hbc >> u) & 1u) {
+                    if (u > fh) emit(run_h, run);  // the previous head's segment ends here
+                    run = v[u];
+                    ++run_h;
+                } else {
+                    run = op.combine(run, v[u]);
                 }
-                f |= fu;
             }
-        }
-        const T in_x = op.shfl_up(x, 1);
-        const int in_h = __shfl_up(xh, 1, kWave);
-        if (valid_lane) {
-            if (lane > 0 && fh < kMergeEpl) emit(in_h, fh > 0 ? op.combine(in_x, pre) : in_x);
-            if (kMergeEpl * (lane + 1) >= n) {  // the task's last segment ends here
-                if (fh < kMergeEpl) emit(run_h, run);
-                else emit(in_h, lane > 0 ? op.combine(in_x, pre) : pre);
+            const T in_x = scan_in(fh < kMergeEpl ? run : pre);
+            if (valid_lane) {
+                if (lane > 0 && fh < kMergeEpl) emit(in_h, fh > 0 ? op.combine(in_x, pre) : in_x);
+                if (kMergeEpl * (lane + 1) >= n) {  // the task's last segment ends here
+                    if (fh < kMergeEpl) emit(run_h, run);
+                    else emit(in_h, lane > 0 ? op.combine(in_x, pre) : pre);
+                }
             }
-        }
-        if (staged) {
+        };
+        // The staged body has no branch on lane data: every step stores, a segment end to its slot and
+        // everything else to the dump slot (as the cold lanes read the identity cell), and the running
+        // sums are selects.  One accumulator serves both as the part before the first head and as the
+        // running segment: a lane without a head leaves the task with its whole fold in it, a lane with
+        // heads with its last head's segment.
+        auto fold_staged = [&]() {
+            const int dump = a.stage;
+            bool seen = (hbc & 1u) != 0u;  // a head at or before this entry
+            int slot = in_h + (int)(hbc & 1u);  // the last head so far
+            T acc = v[0], pre = op.identity();
+#pragma unroll
+            for (int u = 1; u < kMergeEpl; ++u) {
+                const bool head = ((hbc >> u) & 1u) != 0u;
+                stg[head && seen ? slot : dump] = acc;  // the previous head's segment ends here
+                pre = head && !seen ? acc : pre;
+                const T sum = op.combine(acc, v[u]);
+                acc = head ? v[u] : sum;
+                slot += head ? 1 : 0;
+                seen = seen || head;
+            }
+            pre = seen ? pre : acc;
+            const T in_x = scan_in(acc);
+            const T joined = op.combine(in_x, pre);
+            // the segment that entered from the left ends at this lane's first head
+            stg[valid_lane && lane > 0 && seen ? in_h : dump] = (hbc & 1u) ? in_x : joined;
+            // the task's last segment ends in its last lane
+            const bool last = valid_lane && kMergeEpl * (lane + 1) >= n;
+            const T whole = lane > 0 ? joined : pre;
+            stg[last ? (seen ? slot : in_h) : dump] = seen ? acc : whole;
             // the window is wave-private and LDS runs a wave's instructions in order: the fences only
             // keep the compiler from moving these reads above the writes (or the next task's writes
             // above these reads)
@@ -611,6 +687,12 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        };
+        if constexpr (LDS) {
+            if (staged) fold_staged();
+            else fold_direct();
+        } else {
+            fold_direct();
         }
         if (kn >= ntask) break;
         k = kn;
@@ -757,6 +839,8 @@ void launch_pull(const Csr& csr, const PullPlan& plan, const Op& op, typename Op
                  bool skip_empty = false, const uint32_t* const* task_live = nullptr, int64_t caller_rows = 0) {
     using T = typename Op::T;
     const bool split = tune().pull_split && plan.split_rows > 0 && split_partial != nullptr;
+    if (task_live != nullptr && !op_task_live<Op>::value)
+        fail(JG_ERR_UNSUPPORTED, "launch_pull: this Op does not declare kTaskLive");
     size_t band0 = 0;  // the first band this call merges
     if (caller_rows > 0) {
         while (band0 < plan.bands.size() && plan.bands[band0]->row_end <= caller_rows) ++band0;
@@ -778,6 +862,12 @@ void launch_pull(const Csr& csr, const PullPlan& plan, const Op& op, typename Op
             JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 24>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
             JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 32>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
+            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 20, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
+            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 24, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
+            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 32, true>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
             attr = true;
         }
@@ -805,7 +895,8 @@ void launch_pull(const Csr& csr, const PullPlan& plan, const Op& op, typename Op
             // one workgroup per CU, a multiple of S: every sub-slice gets grid / S of them
             const unsigned grid = (unsigned)std::max<int64_t>(S, (int64_t)device_cu_count() / S * S);
             // shared equally by the segments; a segment's hot part stays below its stride
-            const int64_t stage_bytes = (int64_t)kMergeWaves * stage * (int64_t)sizeof(T);
+            // (each wave's window: its staging slots and the dump slot)
+            const int64_t stage_bytes = (int64_t)kMergeWaves * (stage + 1) * (int64_t)sizeof(T);
             const int64_t hot_max = (int64_t)((kMergeLdsBytes - stage_bytes - 16) / (int64_t)sizeof(T) - 16) * S;
             HotSegs hs;
             hs.tbits = plan.seg_tbits;
@@ -815,7 +906,11 @@ void launch_pull(const Csr& csr, const PullPlan& plan, const Op& op, typename Op
             const int temporal = tune().merge_temporal == 2 || (tune().merge_temporal == 1 && plan.temporal);
             const size_t lds = hs.hs > 0 ? (size_t)(hs.nseg * (hs.hs / S) + 1) * sizeof(T) + (size_t)stage_bytes + 16 : 0;
             auto go = [&](auto kern) { kern<<<grid, kMergeThreads, lds, s>>>(ma, op, part, carry, hs, temporal); };
-            if (hs.hs > 0) {
+            if (hs.hs > 0 && hs.nseg > 1) {
+                if (bd.width == 20) go(pull_merge_kernel<Op, true, 20, true>);
+                else if (bd.width == 24) go(pull_merge_kernel<Op, true, 24, true>);
+                else go(pull_merge_kernel<Op, true, 32, true>);
+            } else if (hs.hs > 0) {
                 if (bd.width == 20) go(pull_merge_kernel<Op, true, 20>);
                 else if (bd.width == 24) go(pull_merge_kernel<Op, true, 24>);
                 else go(pull_merge_kernel<Op, true, 32>);

@@ -470,6 +470,7 @@ __global__ __launch_bounds__(kBlock) void bfs_init_roots_kernel(int32_t* __restr
 constexpr int kMsLevelWords = 12;
 struct MsBfsOp {
     using T = unsigned long long;
+    static constexpr bool kTaskLive = true;  // launch_pull gets the per-band task bitmaps (msbfs_task_live_kernel)
     const T* __restrict__ F;    // frontier words of the previous level, full length
     T* __restrict__ Fout;       // full length, owned slice written
     T* __restrict__ visited;    // [rows]
@@ -494,7 +495,6 @@ struct MsBfsOp {
     __device__ __forceinline__ T gather(int32_t c) const { return F[c]; }
     __device__ __forceinline__ const T* vec() const { return F; }
     __device__ __forceinline__ T shfl_xor(T v, int o) const { return __shfl_xor(v, o, kWave); }
-    __device__ __forceinline__ T shfl_up(T v, int d) const { return __shfl_up(v, d, kWave); }
     __device__ __forceinline__ bool active(int64_t row) const { return (~visited[row] & *live) != 0ull; }
     // masking with live also discards what a done row's skipped merge tasks left in its partials
     __device__ __forceinline__ void finalize(int64_t row, T acc) const {
