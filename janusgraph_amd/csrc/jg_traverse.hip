@@ -3022,6 +3022,974 @@ void bfs_kept_row(Graph& g, int s, int32_t* depth_out) {
     for (auto& sp : g.shards) rows_to_dense(g, *sp, sp->kept_depth.peer() + (int64_t)s * sp->rows, depth_out);
 }
 
+namespace {
+// ---------------- the engines behind bfs_run ----------------
+// Each fills ctx.last and delivers the caller's rows (depth_rows, nullable) and the kept rows.
+
+// one source, BOTH, over the shards of a halo plan
+void bfs_sharded_do(Graph& g, const int64_t* source_vids, int max_depth, int32_t* const* depth_rows, bool keep) {
+    Ctx& ctx = *g.ctx;
+    int shard = -1;
+    const int64_t l = local_of_vid(g, source_vids[0], &shard);
+    double edges = 0;
+    float ms = 0;
+    const int levels = dobfs_sharded(g, l >= 0 ? shard : -1, l, max_depth, &edges, &ms);
+    ctx.last.compute_ms = ms;
+    ctx.last.levels = levels;
+    ctx.last.supersteps = levels;
+    ctx.last.edges_traversed = l >= 0 ? edges / 2 : 0;
+    if (depth_rows && depth_rows[0])
+        for (auto& sp : g.shards) rows_to_dense(g, *sp, sp->bfs_depth.peer(), depth_rows[0]);
+    if (keep) keep_depth_rows(g);
+}
+
+// one source on one shard
+void bfs_single(Graph& g, const int64_t* source_vids, int direction, int max_depth, int32_t* const* depth_rows,
+                bool keep, Event& t0, Event& t1) {
+    Ctx& ctx = *g.ctx;
+    Shard& sh = *g.shards[0];
+    const BfsCsrs c = pick_csrs(sh, direction);
+    int shard = 0;
+    const int64_t l = local_of_vid(g, source_vids[0], &shard);
+    if (sh.bfs_depth.size() != (size_t)std::max<int64_t>(sh.rows, 1)) {
+        sh.bfs_depth.alloc(std::max<int64_t>(sh.rows, 1));
+        sh.bfs_depth_tail_clean = false;
+    }
+    DevBuf<int32_t>& depth = sh.bfs_depth;
+    int levels = 0;
+    double edges = 0;
+    if (l < 0) {
+        fill_i32_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(depth.get(), sh.rows, -1);
+        JG_LAUNCH_CHECK();
+        sh.bfs_depth_tail_clean = true;
+        JG_HIP(hipEventRecord(t0, sh.stream));
+        JG_HIP(hipEventRecord(t1, sh.stream));
+    } else {
+        bfs_buffers(sh);
+        if (c.pull) bfs_first_col(sh, *c.pull);
+        // BOTH: rows of the empty suffix (no entry) are never reached, so their depths stay -1 from one
+        // traversal to the next and the init skips them, whatever the caller wants back (the
+        // depth output and kept rows no longer pay a longer init than want=False).  The suffix is filled
+        // once, before t0; a source inside it (an isolated vertex) takes the full init and leaves its 0
+        // behind, so the next traversal refills.
+        const int64_t live = c.push == c.pull && c.pull->empty_from >= 0 ? std::min(sh.rows, c.pull->empty_from)
+                                                                          : sh.rows;
+        if (live < sh.rows && !sh.bfs_depth_tail_clean) {
+            fill_i32_kernel<<<grid_for(sh.rows - live), kBlock, 0, sh.stream>>>(depth.get() + live, sh.rows - live, -1);
+            JG_LAUNCH_CHECK();
+        }
+        const bool full_init = l >= live;
+        region_mark(sh.stream, true);
+        JG_HIP(hipEventRecord(t0, sh.stream));
+        levels = dobfs_single(ctx, sh, c, l, max_depth, depth.get(), &edges, nullptr, t1, full_init);
+        sh.bfs_depth_tail_clean = !full_init || live == sh.rows;
+    }
+    JG_HIP(hipEventSynchronize(t1));
+    float ms = 0;
+    JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    ctx.last.compute_ms = ms;
+    ctx.last.levels = levels;
+    ctx.last.supersteps = levels;
+    ctx.last.edges_traversed = direction == JG_DIR_BOTH ? edges / 2 : edges;
+    const Csr* degcsr = c.push ? c.push : c.pull;
+    ctx.last.algorithmic_bytes = 4.0 * (double)degcsr->nnz + 12.0 * (double)sh.rows;
+    if (depth_rows && depth_rows[0]) rows_to_dense(g, sh, depth.get(), depth_rows[0]);
+    if (keep) keep_depth_rows(g);
+}
+
+// 2..8 sources on one shard: the narrow engine (jg_narrow.hip), one frontier byte per row
+void bfs_narrow(Graph& g, const int64_t* source_vids, int nsrc, int direction, int max_depth,
+                int32_t* const* depth_rows, bool keep) {
+    Ctx& ctx = *g.ctx;
+    Shard& sh = *g.shards[0];
+    const BfsCsrs c = pick_csrs(sh, direction);
+    std::vector<int64_t> loc((size_t)nsrc);
+    std::vector<int> shard((size_t)nsrc);
+    locals_of_vids(g, source_vids, nsrc, loc.data(), shard.data());
+    DevBuf<int32_t> planes;
+    if (depth_rows || keep) planes.alloc(std::max<int64_t>((int64_t)nsrc * sh.rows, 1));
+    const NarrowRun r = narrow_bfs(ctx, sh, *c.push, *c.pull, loc.data(), nsrc, max_depth,
+                                   planes.size() ? planes.get() : nullptr);
+    ctx.last.compute_ms = r.ms;
+    ctx.last.levels = r.levels;
+    ctx.last.supersteps = r.levels;
+    ctx.last.edges_traversed = r.entries;
+    ctx.last.algorithmic_bytes = r.bytes;
+    if (depth_rows)
+        for (int s = 0; s < nsrc; ++s)
+            if (depth_rows[s]) rows_to_dense(g, sh, planes.get() + (size_t)s * sh.rows, depth_rows[s]);
+    if (keep) {
+        sh.kept_depth.swap(planes);
+        g.kept_nsrc = nsrc;
+    }
+}
+
+// ---------------- the bit-parallel 64-source BFS driver ----------------
+
+// One shard's state for one batch of at most 64 sources, and what is constant over the batch.
+struct MsBfsShard {
+    Shard* sh = nullptr;
+    BfsCsrs c{};
+    const PullPlan* plan = nullptr;  // the pull adjacency's
+    uint32_t adj = 0;                // the pull adjacency as the key of the gathered vector's layout (adj_of)
+    VecPos pos{};                    // own row -> its slot in the gathered vector
+    int64_t live_rows = 0;           // rows [0, live_rows) have pull entries (pull_live_rows)
+
+    DevBuf<unsigned long long> F[2], vis;
+    DevBuf<int32_t> depth, changed;  // depth: int32 planes once widened
+    DevBuf<uint8_t> depth8;           // byte planes of levels kMsLevelWords .. 254 (allocated on reaching them)
+    DevBuf<unsigned long long> nwl;   // [kMsLevelWords][rows] new-bit words of levels 0 .. kMsLevelWords-1
+    DevBuf<unsigned long long> hub, split;
+    DevBuf<unsigned long long> live;  // [0] the pull level's live bits, [1] all sources (top-down)
+    DevBuf<unsigned long long> xrest;  // msbfs_exit: the rows pass B scans (a bit per row)
+    MsBu bx{};                         // msbfs_exit: every row with entries (bx.rows 0: off on this shard)
+    int64_t exit_tasks = 0;            // band 0's merge tasks (its live count decides an exit level)
+    int exit_all_levels = 0;
+    // merge tasks of the bands the exit kernels took instead (on levels that count every task, and on all)
+    double exit_unskipped_tasks = 0, exit_level_tasks = 0;
+    unsigned long long b0_live_merged = 0;     // msbfs_exit 1: band 0's live tasks of levels that merged it
+    double xlive_permille = 1000.0;            // the last probe's live share of band 0's tasks
+    std::vector<DevBuf<unsigned long long>> todo, tlive;  // per band: row and task bitmaps
+    DevBuf<int64_t> dloc;             // [64] each source's own row (-1: another shard's)
+    // levels recorded as (row, new word) records instead of nwl words (level 0 from the sources and
+    // every top-down level below kMsLevelWords): {level, count, rows, words}
+    struct Rec {
+        int level = 0;
+        int64_t n = 0;
+        DevBuf<int32_t> rows;
+        DevBuf<unsigned long long> words;
+    };
+    std::vector<Rec> recs;
+    DevBuf<unsigned long long> work;  // [0] live merge tasks over all pull levels, [1] reached pairs,
+                                      // [2] entries the early-exit bottom-up levels scanned,
+                                      // [3] band 0's live tasks of this level (msbfs_exit 1)
+    int64_t light_nnz = 0, all_tasks = 0;  // entries outside the split, merge tasks of all bands
+
+    // the top-down levels' buffers (allocated when the batch may run one)
+    DevBuf<int32_t> queue[2], touched;
+    DevBuf<int64_t> qoff[2], touched_off;
+    DevBuf<unsigned long long> ctr;   // [0] frontier, [1] touched, [2] halo slots set
+    DevBuf<int64_t> srcs;             // the shard's distinct source rows
+    DevBuf<unsigned long long> rbuf;  // sharded: the peers' halo slots for own rows (send-list order)
+    DevBuf<unsigned long long> hs;    // sharded: halo staging (compact positions), zero between levels
+    DevBuf<int32_t> hlist;            // sharded: the staging slots a level set
+    DevBuf<int64_t> hlist_off;        // appender scratch
+    DevBuf<unsigned int> bcount;      // [kRedBlocks][P] set staging slots per histogram block and peer
+    DevBuf<unsigned long long> pairs, rpairs, pcnt;  // sparse reverse exchange: sent / received
+                                                     // (offset, word) pairs, per-peer counts + cursors
+    std::vector<int64_t> src_rows;
+    int64_t nq = 0, mf = 0;
+    int64_t nrp = 0;                  // pairs received by the last sparse exchange
+    PairRuns pv{};                    // their per-peer runs and this shard's send-list offsets
+    int64_t nq_in = 0;                // the last top-down level's input frontier (its queue)
+    bool rowapply = false;            // this level's apply passes over every row (no touched list)
+};
+
+// One batch of at most 64 sources: a bit per source in every frontier / visited word.  Works sharded
+// (frontier words allgathered, or pushed over the halo plan).  The constructor does what comes before
+// the timed region, run() is the timed region, add_work() and deliver() come after it; the buffers live
+// as long as the object.
+class MsBfsBatch {
+public:
+    MsBfsBatch(Graph& graph, int dir, const int64_t* vids, int nsrc)
+        : g(graph), ctx(*graph.ctx), sh0(*graph.shards[0]), direction(dir), ns(nsrc),
+          full(nsrc == 64 ? ~0ull : ((1ull << nsrc) - 1ull)), sv(graph.shards.size()), src_local((size_t)nsrc),
+          src_shard((size_t)nsrc) {
+        for (size_t i = 0; i < sv.size(); ++i) {
+            MsBfsShard& s = sv[i];
+            s.sh = &*g.shards[i];
+            s.c = pick_csrs(*s.sh, direction);
+            s.plan = s.c.pull == &s.sh->both ? &s.sh->plan_both : &s.sh->plan_in;
+            s.adj = adj_of(*s.sh, s.c);
+            s.pos = g.vec_pos(*s.sh, s.adj);
+            s.live_rows = pull_live_rows(*s.sh, s.c);
+        }
+        const BfsCsrs& c0 = sv[0].c;
+        // Levels whose frontier has few edges run top-down: on one shard with a push adjacency, and
+        // on a sharded BOTH traversal over the halo plan (msbfs_td 1; 2 = one shard only).  Sharded,
+        // a shard pushes its own frontier rows; bits for a peer's vertex collect in its halo slot and
+        // go to the owner by the reverse halo exchange (msbfs_td_recv_kernel).
+        td_one = g.shards.size() == 1 && g.P == 1 && c0.push != nullptr && tune().msbfs_td != 0;
+        td_shard = g.P > 1 && g.P <= kMaxPeersMs && direction == JG_DIR_BOTH && sh0.halo_both.on &&
+                   tune().msbfs_td == 1;
+        td_ok = td_one || td_shard;
+        locals_of_vids(g, vids, ns, src_local.data(), src_shard.data());
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            const PullPlan& plan = *s.plan;
+            if (!s.c.pull) fail(JG_ERR_UNSUPPORTED, "multi-source BFS needs the pull adjacency");
+            if (s.c.pull == &sh.out) fail(JG_ERR_UNSUPPORTED, "multi-source IN traversal is not supported");
+            if (s.c.push) push_nnz += s.c.push->nnz;
+            const int64_t len = g.vec_len(sh, s.adj);
+            s.F[0].alloc(len);
+            s.F[1].alloc(len);
+            s.vis.alloc(std::max<int64_t>(sh.rows, 1));
+            s.nwl.alloc(std::max<int64_t>(sh.rows * kMsLevelWords, 1));
+            s.changed.alloc(1);
+            s.hub.alloc(std::max<int64_t>(plan.num_chunks, 1));
+            if (tune().msbfs_split && plan.split_rows > 0) s.split.alloc(plan.split_partial_len());
+            s.live.alloc(3);  // [2]: a split level's pull live bits
+            s.work.alloc(4);
+            JG_HIP(hipMemsetAsync(s.work.get(), 0, 4 * sizeof(unsigned long long), sh.stream));
+            if (tune().msbfs_exit > 0 && s.split.size() && !plan.bands.empty())
+                s.xrest.alloc(std::max<int64_t>((sh.rows + 63) / 64, 1));
+            s.light_nnz = s.c.pull->nnz;
+            if (s.split.size() && plan.split_rows > 0) {
+                int64_t split_nnz = 0;
+                copy_d2h(&split_nnz, s.c.pull->row_ptr.get() + plan.split_rows, sizeof split_nnz, sh.stream);
+                s.light_nnz -= split_nnz;
+                for (const auto& bd : plan.bands) s.all_tasks += bd->tasks;
+            }
+            const unsigned long long lw[2] = {full, full};
+            copy_h2d(s.live.get(), lw, sizeof lw, sh.stream);
+            if (s.split.size() && tune().msbfs_skip) {
+                s.todo.resize(plan.bands.size());
+                s.tlive.resize(plan.bands.size());
+                for (size_t b = 0; b < plan.bands.size(); ++b) {
+                    s.todo[b].alloc(std::max<int64_t>((plan.bands[b]->rows() + 63) / 64, 1));
+                    s.tlive[b].alloc(std::max<int64_t>((plan.bands[b]->tasks + 63) / 64, 1));
+                }
+            }
+            std::vector<int64_t> loc(ns, -1);
+            for (int q = 0; q < ns; ++q)
+                if (src_local[(size_t)q] >= 0 && src_shard[(size_t)q] == sh.index) loc[q] = src_local[(size_t)q];
+            // the shard's distinct source rows: its first top-down queue (msbfs_source_queue_kernel)
+            for (int64_t l : loc)
+                if (l >= 0 && std::find(s.src_rows.begin(), s.src_rows.end(), l) == s.src_rows.end())
+                    s.src_rows.push_back(l);
+            s.dloc.alloc(ns);
+            copy_h2d(s.dloc.get(), loc.data(), ns * sizeof(int64_t), sh.stream);
+            JG_HIP(hipStreamSynchronize(sh.stream));
+        });
+        allreduce_sum_i64(g, &push_nnz, 1);
+        need_fwd = g.P > 1;
+        if (td_ok)  // allocated before the timed region (~2.3 GB at RMAT-26 on one shard)
+            each([&](MsBfsShard& s) {
+                Shard& sh = *s.sh;
+                const size_t r1 = (size_t)std::max<int64_t>(sh.rows, 1);
+                for (int k = 0; k < 2; ++k) {
+                    s.queue[k].alloc(r1);
+                    s.qoff[k].alloc(r1);
+                }
+                s.touched.alloc(r1);
+                s.touched_off.alloc(r1);
+                s.ctr.alloc(3);
+                s.srcs.alloc(std::max<size_t>(s.src_rows.size(), 1));
+                if (!s.src_rows.empty())
+                    copy_h2d(s.srcs.get(), s.src_rows.data(), s.src_rows.size() * sizeof(int64_t), sh.stream);
+                if (td_shard) {
+                    const Halo& h = sh.halo_both;
+                    s.rbuf.alloc(std::max<int64_t>(h.send_off[g.P], 1));
+                    s.hs.alloc(g.vec_len(sh, JG_ADJ_BOTH));
+                    s.hlist.alloc(std::max<int64_t>(h.recv_off[g.P], 1));
+                    s.hlist_off.alloc(std::max<int64_t>(h.recv_off[g.P], 1));
+                    if (tune().msbfs_sparse) {
+                        s.pairs.alloc(2 * std::max<int64_t>(h.recv_off[g.P], 1));
+                        s.rpairs.alloc(2 * std::max<int64_t>(h.send_off[g.P], 1));
+                        s.pcnt.alloc(2 * (size_t)g.P);
+                        s.bcount.alloc((size_t)kRedBlocks * g.P);
+                    }
+                }
+            });
+        for (MsBfsShard& s : sv)  // the early exit's first columns (before t0)
+            if (s.c.pull) bfs_first_col(*s.sh, *s.c.pull);
+        // msbfs_exit: every row with entries scans its row with early exit (msbfs_exit_first_kernel /
+        // msbfs_exit_rest_kernel) on pull levels where few of band 0's merge tasks are live, and such a
+        // level runs no merge launch at all.  On the level after the frontier's peak a hub row finds all
+        // its unvisited live bits within its first entries: RMAT-22, band 0 examines 0.1% instead of
+        // 27.3% of the entries (tools/msbfs_exit_sim.py).  Band 0's live tasks alone decide
+        // (every exit band's bitmaps took the same decisions, round 4); each shard decides for its own
+        // rows.  (Only the exit bands through the exit, the light rows merged: RMAT-26 11.42 vs 11.20 ms.)
+        each([&](MsBfsShard& s) {
+            const PullPlan& plan = *s.plan;
+            if (tune().msbfs_exit > 0 && tune().pull_split && plan.split_rows > 0 && !plan.bands.empty() &&
+                s.xrest.size() > 0 && plan.bands[0]->row_begin == 0 && plan.bands[0]->row_end > 0) {
+                s.bx.rp = s.c.pull->row_ptr.get();
+                s.bx.col = s.c.pull->col.get();
+                s.bx.first_col = bfs_first_col(*s.sh, *s.c.pull);
+                s.bx.rows = s.live_rows;  // the rows a pull level finalises (those with entries)
+                s.bx.examined = s.work.get() + 2;
+                s.bx.first = tune().msbfs_exit_first;
+                s.exit_tasks = plan.bands[0]->tasks;
+            }
+        });
+        queued = td_ok;
+        word_levels = td_ok ? 0u : 1u;
+    }
+
+    // The timed region (t0 .. t1, recorded on the first shard's stream); returns the levels run.
+    int run(int max_depth, Event& t0, Event& t1) {
+        prof_discard_exchanges(g);  // exchange pairs never straddle t0
+        region_mark(sh0.stream, true);
+        JG_HIP(hipEventRecord(t0, sh0.stream));
+        init_state();
+        while (max_depth < 0 || level < max_depth) {
+            if (level + 1 >= kMsLevelWords) ensure_depth8();
+            if (level + 1 >= 255) widen();
+            const bool td_level = td_ok && (double)g_mf < (double)push_nnz / (double)tune().bfs_alpha;
+            // a pull level (merge engine or the exit kernels) finalises every own row: its words need no clearing
+            if (!td_level && level + 1 < kMsLevelWords) word_levels |= 1u << (level + 1);
+            if (td_level && !queued) {
+                build_frontier(qc ^ 1);
+                qc ^= 1;
+            }
+            const bool have_live = live_ready;
+            queued = live_ready = false;
+            if (td_level)
+                top_down_level();
+            else
+                pull_level(have_live);
+            int32_t any = 0;
+            if (td_ok) {
+                // the level's new frontier (counted over all shards and ranks by read_frontier) is
+                // exactly the rows that gained a bit: no read-back of the changed flags
+                any = g_nq > 0;
+            } else {
+                each([&](MsBfsShard& s) {
+                    int32_t ch = 0;
+                    JG_HIP(hipMemcpyAsync(&ch, s.changed.get(), sizeof ch, hipMemcpyDeviceToHost, s.sh->stream));
+                    JG_HIP(hipStreamSynchronize(s.sh->stream));
+                    any |= ch;
+                });
+                any = allreduce_or(g, any);
+            }
+            cur ^= 1;
+            ++level;
+            if (!any) break;
+        }
+        JG_HIP(hipEventRecord(t1, sh0.stream));
+        region_mark(sh0.stream, false);
+        return level;
+    }
+
+    // The work of this batch, counted after its timed region: per pull level 12 B per entry of a
+    // live merge task (col + gathered frontier word; a task streams its 512 slots) and of the light
+    // rows, 32 B per row (visited, the new frontier word, the level's new-bit word, the next
+    // level's live scan); per top-down level 12 B per frontier entry, 24 B per touched word and 8 B
+    // per queued vertex; past kMsLevelWords levels 4 B per reached (source, row) pair (a plane entry)
+    void add_work(double& bytes, double& entries) {
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            // one shard, BOTH: the visited words past the empty suffix were not cleared (the init); there only
+            // the source rows hold bits, one per source
+            const int64_t prow = td_one && s.c.pull == s.c.push ? s.live_rows : sh.rows;
+            if (level >= kMsLevelWords) {  // the plane entries are counted only when planes were written
+                msbfs_pairs_kernel<<<red_grid(prow), kRedThreads, 0, sh.stream>>>(s.vis.get(), prow, s.work.get() + 1);
+                JG_LAUNCH_CHECK();
+            }
+            unsigned long long w[3] = {0, 0, 0};
+            copy_d2h(w, s.work.get(), sizeof w, sh.stream);
+            if (level >= kMsLevelWords && prow < sh.rows)
+                for (int q = 0; q < ns; ++q)
+                    if (src_local[(size_t)q] >= prow && src_shard[(size_t)q] == sh.index) ++w[1];
+            const double live_tasks = s.todo.empty() ? (double)s.all_tasks * pull_levels - s.exit_level_tasks
+                                                      : (double)w[0] +
+                                                            (double)s.b0_live_merged +
+                                                            (double)s.all_tasks * unskipped_levels -
+                                                            s.exit_unskipped_tasks;
+            const double e = live_tasks * kMergeTask + (double)s.light_nnz * (pull_levels - s.exit_all_levels) + (double)w[2];
+            entries += e;
+            bytes += 12.0 * e + 32.0 * (double)sh.rows * pull_levels +
+                     (level >= kMsLevelWords ? 4.0 * (double)w[1] : 0.0);
+        });
+        entries += td_entries;
+        bytes += 12.0 * td_entries + 24.0 * td_touched + 8.0 * td_queued + 8.0 * td_row_passes;
+    }
+
+    // The caller's int32 rows (rows: this batch's, nullable, each nullable) and the kept planes: the
+    // widened byte / int32 planes, then the word-recorded levels.
+    void deliver(int32_t* const* rows, bool keep) {
+        if (!rows && !keep) return;
+        widen();
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            const int lw = std::min(level + 1, kMsLevelWords);
+            if (sh.rows > 0) {
+                msbfs_levels_to_planes_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(
+                    s.nwl.get(), lw, word_levels, sh.rows, s.live_rows, ns, s.depth.get());
+                JG_LAUNCH_CHECK();
+            }
+            for (const auto& r : s.recs)
+                if (r.n > 0 && r.level < lw) {
+                    msbfs_records_to_planes_kernel<<<grid_for(r.n), kBlock, 0, sh.stream>>>(
+                        r.rows.get(), r.words.get(), r.n, r.level, sh.rows, ns, s.depth.get());
+                    JG_LAUNCH_CHECK();
+                }
+            JG_HIP(hipStreamSynchronize(sh.stream));
+        });
+        if (rows)
+            for (MsBfsShard& s : sv)
+                for (int q = 0; q < ns; ++q)
+                    if (rows[q]) rows_to_dense(g, *s.sh, s.depth.peer() + (size_t)q * s.sh->rows, rows[q]);
+        if (keep)  // the planes stay with their shards (jg_bfs_kept_row)
+            for (MsBfsShard& s : sv) s.sh->kept_depth.swap(s.depth);
+    }
+
+private:
+    // f(shard state) for every local shard, on its device
+    template <class F>
+    void each(F&& f) {
+        for (MsBfsShard& s : sv) {
+            DeviceGuard dg(*s.sh);
+            f(s);
+        }
+    }
+
+    // touched (nullable): += the rows the top-down level just applied (its touched counter)
+    void read_frontier(double* touched = nullptr) {
+        int64_t v[2] = {0, 0};
+        each([&](MsBfsShard& s) {
+            unsigned long long hh[2] = {0, 0};
+            copy_d2h(hh, s.ctr.get(), (touched ? 2 : 1) * sizeof(unsigned long long), s.sh->stream);
+            const unsigned long long h = hh[0];
+            if (touched) *touched += (double)(hh[1] >> kPackShift);
+            s.nq = (int64_t)(h >> kPackShift);
+            s.mf = (int64_t)(h & kEdgeMask);
+            v[0] += s.nq;
+            v[1] += s.mf;
+        });
+        allreduce_sum_i64(g, v, 2);
+        g_nq = v[0];
+        g_mf = v[1];
+    }
+
+    // live bits of the next pull level from every shard's own rows (the top-down apply or the scan
+    // after a pull level ORed them into live[0]): OR over the local shards and the ranks, a superset
+    // of what the shard's gathered vector holds, which is all the task skip needs
+    void combine_live() {
+        if (g.shards.size() == 1 && ctx.nranks == 1) return;
+        uint64_t v = 0;
+        each([&](MsBfsShard& s) {
+            uint64_t w = 0;
+            copy_d2h(&w, s.live.get(), sizeof w, s.sh->stream);
+            v |= w;
+        });
+        v = allreduce_or_u64(g, v);
+        each([&](MsBfsShard& s) { copy_h2d(s.live.get(), &v, sizeof v, s.sh->stream); });
+    }
+
+    void build_frontier(int qslot) {
+        each([&](MsBfsShard& s) {
+            const int64_t ne = s.live_rows;
+            JG_HIP(hipMemsetAsync(s.ctr.get(), 0, sizeof(unsigned long long), s.sh->stream));
+            msbfs_frontier_kernel<<<grid_for(ne), kBlock, 0, s.sh->stream>>>(
+                s.F[cur].get(), ne, s.c.push->row_ptr.get(), s.queue[qslot].get(), s.qoff[qslot].get(), s.ctr.get());
+            JG_LAUNCH_CHECK();
+        });
+        read_frontier();
+    }
+
+    // Depths: levels 0 .. kMsLevelWords-1 as new-bit words (nwl), levels up to 254 as byte planes
+    // (allocated, all 255 = unreached, when the traversal reaches them), beyond as int32 planes (a
+    // traversal about to write level 255 widens the byte planes first)
+    void ensure_depth8() {
+        each([&](MsBfsShard& s) {
+            if (s.depth8.size() || s.depth.size()) return;
+            s.depth8.alloc(std::max<int64_t>(s.sh->rows * ns, 1));
+            JG_HIP(hipMemsetAsync(s.depth8.get(), 0xFF, s.depth8.bytes(), s.sh->stream));
+        });
+    }
+    void widen() {
+        each([&](MsBfsShard& s) {
+            if (s.depth.size()) return;
+            Shard& sh = *s.sh;
+            const int64_t total = std::max<int64_t>(sh.rows * ns, 1);
+            s.depth.alloc(total);
+            if (s.depth8.size()) {
+                msbfs_widen_kernel<<<grid_for(total), kBlock, 0, sh.stream>>>(s.depth8.get(), total, s.depth.get());
+                JG_LAUNCH_CHECK();
+            } else {
+                fill_i32_kernel<<<grid_for(total), kBlock, 0, sh.stream>>>(s.depth.get(), total, -1);
+                JG_LAUNCH_CHECK();
+            }
+            JG_HIP(hipStreamSynchronize(sh.stream));
+            s.depth8.reset();
+        });
+    }
+
+    // the fields of a level's operator that a pull level and a top-down apply share (the caller sets nwl,
+    // changed and live)
+    MsBfsOp make_op(const MsBfsShard& s, int lvl) const {
+        MsBfsOp op{};
+        op.F = s.F[cur].get();
+        op.Fout = s.F[cur ^ 1].get();
+        op.visited = s.vis.get();
+        op.depth = s.depth.get();
+        op.depth8 = s.depth8.get();
+        op.rows = s.sh->rows;
+        op.pos = s.pos;
+        op.lvl = lvl;
+        return op;
+    }
+
+    // The call's state, inside the timed region: frontiers, visited bits, the halo staging, the
+    // sources (and level 0's depth record), then the level-0 frontier
+    void init_state() {
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            if (td_one && s.c.pull == s.c.push) {
+                // one shard, BOTH: only rows before the empty suffix are read after level 0 (no gather,
+                // push target, scan, apply or finalise reaches the rows past it, §5; a directed traversal
+                // gathers columns without pull entries of their own, so it clears everything); the source
+                // rows among them get their words stored by the init below.  RMAT-26 BOTH: 34 of 67 M rows,
+                // three 537 MB clears halved
+                const int64_t ne = s.live_rows, base = s.pos.base;
+                if (std::getenv("JG_MSBFS_POISON") && ne < sh.rows) {  // (test switch: garbage past the suffix)
+                    const size_t tail = (size_t)(sh.rows - ne) * sizeof(unsigned long long);
+                    JG_HIP(hipMemsetAsync(s.F[0].get() + base + ne, 0xA5, tail, sh.stream));
+                    JG_HIP(hipMemsetAsync(s.F[1].get() + base + ne, 0x5A, tail, sh.stream));
+                    JG_HIP(hipMemsetAsync(s.vis.get() + ne, 0xC3, tail, sh.stream));
+                }
+                JG_HIP(hipMemsetAsync(s.F[0].get() + base, 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
+                JG_HIP(hipMemsetAsync(s.F[1].get() + base, 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
+                JG_HIP(hipMemsetAsync(s.vis.get(), 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
+            } else {
+                zero_gathered(g, sh, s.adj, s.F[0].get(), sizeof(unsigned long long));
+                zero_gathered(g, sh, s.adj, s.F[1].get(), sizeof(unsigned long long));
+                JG_HIP(hipMemsetAsync(s.vis.get(), 0, s.vis.bytes(), sh.stream));
+            }
+            if (s.hs.size()) zero_gathered(g, sh, JG_ADJ_BOTH, s.hs.get(), sizeof(unsigned long long));
+            MsBfsShard::Rec* r0 = nullptr;
+            if (td_ok) {  // level 0 as records of the source rows
+                s.recs.emplace_back();
+                r0 = &s.recs.back();
+                r0->level = 0;
+                r0->n = ns;
+                r0->rows.alloc(ns);
+                r0->words.alloc(ns);
+            } else {  // level 0's words
+                JG_HIP(hipMemsetAsync(s.nwl.get(), 0, (size_t)sh.rows * sizeof(unsigned long long), sh.stream));
+            }
+            msbfs_init_kernel<<<1, kWave, 0, sh.stream>>>(s.dloc.get(), ns, s.F[0].get(), s.vis.get(),
+                                                      r0 ? nullptr : s.nwl.get(), sh.rows, s.pos,
+                                                      r0 ? r0->rows.get() : nullptr, r0 ? r0->words.get() : nullptr);
+            JG_LAUNCH_CHECK();
+        });
+        if (!td_ok) {
+            std::vector<void*> bufs;
+            for (auto& s : sv) bufs.push_back(s.F[0].peer());
+            exchange_vec(g, sv[0].adj, bufs, sizeof(unsigned long long), ncclUint64);
+            need_fwd = false;
+        }
+        if (td_ok) {  // the level-0 frontier is the source rows: queued directly, no scan of F
+            each([&](MsBfsShard& s) {
+                msbfs_source_queue_kernel<<<1, kWave, 0, s.sh->stream>>>(s.srcs.get(), (int)s.src_rows.size(),
+                                                                      s.c.push->row_ptr.get(), s.queue[0].get(),
+                                                                      s.qoff[0].get(), s.ctr.get());
+                JG_LAUNCH_CHECK();
+            });
+            read_frontier();
+        }
+    }
+
+    // A level pushed from the queued frontier rows: every shard's push, the reverse exchange of the
+    // peers' halo slots (sharded), the apply (which builds the next queue), the level's depth records
+    void top_down_level() {
+        std::vector<void*> fv, rv;
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            // changed, the frontier / touched / staging counters, the live bits the apply ORs and the
+            // sparse exchange's per-peer counts and cursors
+            zero_words({{s.changed.get(), sizeof(int32_t)},
+                        {s.ctr.get(), 3 * sizeof(unsigned long long)},
+                        {s.live.get(), sizeof(unsigned long long)},
+                        {s.pcnt.get(), s.pcnt.bytes()}},
+                       sh.stream);
+            // the output's own words start at zero (the first toucher of a word queues it): after a
+            // top-down level only its input queue's words are set, otherwise clear every own row
+            if (prev_td) {
+                if (s.nq_in > 0) {
+                    msbfs_zero_list_kernel<<<grid_for(s.nq_in), kBlock, 0, sh.stream>>>(
+                        s.F[cur ^ 1].get(), s.queue[qc ^ 1].get(), s.nq_in);
+                    JG_LAUNCH_CHECK();
+                }
+            } else if (level > 0) {  // level 0: F[1] is as the init zeroed it
+                // rows without pull entries are never written after level 0: their words are zero
+                // except an isolated source's level-0 word, cleared apart (RMAT-26: 215 of 537 MB
+                // cleared)
+                const int64_t ne = s.live_rows;
+                JG_HIP(hipMemsetAsync(s.F[cur ^ 1].get(), 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
+                if (ne < sh.rows && !s.src_rows.empty()) {
+                    msbfs_zero_tail_sources_kernel<<<1, kWave, 0, sh.stream>>>(
+                        s.F[cur ^ 1].get(), s.srcs.get(), (int)s.src_rows.size(), ne);
+                    JG_LAUNCH_CHECK();
+                }
+            }
+            s.nq_in = s.nq;
+            // a big level (one shard): the apply passes over every row instead of a touched list
+            s.rowapply = !td_shard && tune().msbfs_td_rowapply > 0 && s.mf * tune().msbfs_td_rowapply >= sh.rows;
+            if (s.mf > 0) {
+                MsTd a{s.queue[qc].get(), s.qoff[qc].get(), s.nq, s.mf, s.c.push->row_ptr.get(),
+                       s.c.push->col.get(), s.F[cur].get(), s.vis.get(), s.F[cur ^ 1].get(), s.touched.get(),
+                       s.touched_off.get(), s.ctr.get() + 1, td_shard ? sh.halo_both.tbits : 31,
+                       td_shard ? s.hs.get() : nullptr, s.hlist.get(), s.hlist_off.get(), s.ctr.get() + 2,
+                       td_shard && s.pcnt.size() ? s.pcnt.get() : nullptr, sh.index, g.P,
+                       // the first top-down levels skip the visited probe: next to nothing is visited
+                       // yet, and it is a random 8-byte read per edge (RMAT-26 level 1: 33.6 M)
+                       level >= tune().msbfs_td_noprobe ? 1 : 0, s.rowapply ? 1 : 0};
+                msbfs_td_kernel<<<(unsigned)std::min<int64_t>(std::max<int64_t>(
+                                      (s.mf / kTdEdgesPerThread + kBlock - 1) / kBlock, 1), tune().bfs_grid),
+                                  kBlock, 0, sh.stream>>>(a);
+                JG_LAUNCH_CHECK();
+                if (td_shard && s.pcnt.size()) {  // the set slots per peer (the sparse exchange's sizes)
+                    msbfs_slot_hist_kernel<<<(unsigned)kRedBlocks, kRedThreads, 0, sh.stream>>>(
+                        s.hlist.get(), s.ctr.get() + 2, sh.halo_both.tbits, sh.index, g.P, s.bcount.get(),
+                        s.pcnt.get());
+                    JG_LAUNCH_CHECK();
+                }
+            }
+            fv.push_back(s.hs.peer());
+            rv.push_back(s.rbuf.peer());
+        });
+        const bool sparse_done = td_shard && tune().msbfs_sparse && reverse_exchange_sparse();
+        if (td_shard && !sparse_done) reverse_exchange_dense(fv, rv);
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            // counts stay on the device (the apply and the clearing read them there): one host
+            // read-back per level, read_frontier's
+            if (td_shard) {  // the staging slots went out with the reverse exchange: back to zero
+                msbfs_zero_list_packed_kernel<<<grid_for(sh.halo_both.recv_off[(size_t)g.P]), kBlock, 0, sh.stream>>>(
+                    s.hs.get(), s.hlist.get(), s.ctr.get() + 2);
+                JG_LAUNCH_CHECK();
+            }
+            td_entries += (double)s.mf;
+            if (debug_bfs())
+                std::fprintf(stderr, "[jg msbfs] level %d top-down (shard %d): %lld frontier rows, %lld push entries\n",
+                             level, sh.index, (long long)s.nq, (long long)s.mf);
+            td_queued += (double)s.nq;
+            if (s.rowapply) td_row_passes += (double)s.live_rows;
+            MsBfsOp op = make_op(s, level + 1);
+            op.nwl = nullptr;  // recorded from the next queue below (msbfs_td_record_kernel)
+            op.changed = s.changed.get();
+            op.live = s.live.get() + 1;
+            // (the row-order apply stops at the pull adjacency's empty suffix: a push target has a
+            // pull entry, so no row past it gains a bit after level 0; RMAT-26 BOTH: 34 of 67 M rows)
+            if (s.rowapply)
+                msbfs_td_apply_rows_kernel<<<grid_for(s.live_rows), kBlock, 0, sh.stream>>>(
+                    s.live_rows, op, s.c.push->row_ptr.get(), s.queue[qc ^ 1].get(), s.qoff[qc ^ 1].get(),
+                    s.ctr.get(), s.live.get());
+            else
+                msbfs_td_apply_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(
+                    s.touched.get(), s.ctr.get() + 1, op, s.c.push->row_ptr.get(), s.queue[qc ^ 1].get(),
+                    s.qoff[qc ^ 1].get(), s.ctr.get(), s.live.get());
+            JG_LAUNCH_CHECK();
+        });
+        read_frontier(&td_touched);
+        if (level + 1 < kMsLevelWords)
+            each([&](MsBfsShard& s) {  // the level's depths: its new queue
+                const int64_t nq = s.nq;
+                s.recs.emplace_back();
+                MsBfsShard::Rec& r = s.recs.back();
+                r.level = level + 1;
+                r.n = nq;
+                r.rows.alloc(std::max<int64_t>(nq, 1));
+                r.words.alloc(std::max<int64_t>(nq, 1));
+                if (nq > 0) {
+                    msbfs_td_record_kernel<<<grid_for(nq), kBlock, 0, s.sh->stream>>>(
+                        s.queue[qc ^ 1].get(), nq, s.F[cur ^ 1].get(), s.pos, r.rows.get(), r.words.get());
+                    JG_LAUNCH_CHECK();
+                }
+            });
+        combine_live();
+        qc ^= 1;
+        queued = live_ready = true;
+        need_fwd = td_shard;
+        prev_td = true;
+    }
+
+    // Sparse: only the set staging slots travel, as (offset, word) pairs, when they are fewer
+    // than half the halo slots over all shards (the tail levels and the first levels from
+    // the sources set a few thousand).  Returns whether it ran (otherwise the dense exchange does).
+    bool reverse_exchange_sparse() {
+        const int P = g.P;
+        const size_t ns_ = sv.size();
+        std::vector<std::vector<int64_t>> cnt(ns_, std::vector<int64_t>((size_t)P, 0));
+        std::vector<int64_t> mat((size_t)P * P + 1, 0);
+        for (size_t i = 0; i < ns_; ++i) {
+            Shard& sh = *sv[i].sh;
+            DeviceGuard dg(sh);
+            // per-peer slot counts: the top-down kernel counted the slots it set first
+            std::vector<unsigned long long> c((size_t)P);
+            copy_d2h(c.data(), sv[i].pcnt.get(), (size_t)P * sizeof(unsigned long long), sh.stream);
+            for (int q = 0; q < P; ++q) {
+                cnt[i][(size_t)q] = (int64_t)c[(size_t)q];
+                mat[(size_t)sh.index * P + q] = (int64_t)c[(size_t)q];
+            }
+            mat[(size_t)P * P] += sh.halo_both.recv_off[(size_t)P];  // the dense exchange's words
+        }
+        allreduce_sum_i64(g, mat.data(), P * P + 1);
+        int64_t pairs_all = 0;
+        for (int64_t k = 0; k < (int64_t)P * P; ++k) pairs_all += mat[(size_t)k];
+        if (2 * pairs_all >= mat[(size_t)P * P]) return false;
+        std::vector<const char*> sp(ns_);
+        std::vector<char*> rp(ns_);
+        std::vector<std::vector<int64_t>> so(ns_), sc(ns_), ro(ns_), rc(ns_);
+        for (size_t i = 0; i < ns_; ++i) {
+            MsBfsShard& s = sv[i];
+            Shard& sh = *s.sh;
+            DeviceGuard dg(sh);
+            so[i].assign((size_t)P + 1, 0);
+            ro[i].assign((size_t)P + 1, 0);
+            sc[i].assign((size_t)P, 0);
+            rc[i].assign((size_t)P, 0);
+            PairRuns pk{}, pv{};
+            pk.P = pv.P = P;
+            for (int q = 0; q < P; ++q) {
+                so[i][(size_t)q + 1] = so[i][(size_t)q] + cnt[i][(size_t)q];
+                const int64_t from_q = mat[(size_t)q * P + sh.index];
+                ro[i][(size_t)q + 1] = ro[i][(size_t)q] + from_q;
+                sc[i][(size_t)q] = 2 * cnt[i][(size_t)q];  // uint64 elements: two per pair
+                rc[i][(size_t)q] = 2 * from_q;
+            }
+            for (int q = 0; q <= P; ++q) {
+                pk.off[q] = so[i][(size_t)q];
+                pv.off[q] = ro[i][(size_t)q];
+                pv.send_off[q] = sh.halo_both.send_off[(size_t)q];
+            }
+            const int64_t nh = so[i][(size_t)P];
+            if (nh > 0) {
+                msbfs_pair_pack_kernel<<<(unsigned)kRedBlocks, kRedThreads, 0, sh.stream>>>(
+                    s.hlist.get(), nh, s.hs.get(), sh.halo_both.tbits, sh.index, pk, s.bcount.get(), s.pairs.get());
+                JG_LAUNCH_CHECK();
+            }
+            for (int q = 0; q <= P; ++q) {
+                so[i][(size_t)q] *= 2;
+                ro[i][(size_t)q] *= 2;
+            }
+            sp[i] = reinterpret_cast<const char*>(s.pairs.get());
+            rp[i] = reinterpret_cast<char*>(s.rpairs.get());
+            s.nrp = ro[i][(size_t)P] / 2;
+            s.pv = pv;
+        }
+        exchange_runs(g, sp, so, sc, rp, ro, rc, sizeof(unsigned long long), ncclUint64);
+        each([&](MsBfsShard& s) {
+            if (s.nrp > 0) {
+                msbfs_td_recv_pairs_kernel<<<grid_for(s.nrp), kBlock, 0, s.sh->stream>>>(
+                    s.rpairs.get(), s.nrp, s.pv, s.sh->halo_both.send_src.get(), s.vis.get(), s.F[cur ^ 1].get(),
+                    s.touched.get(), s.touched_off.get(), s.ctr.get() + 1);
+                JG_LAUNCH_CHECK();
+            }
+        });
+        if (debug_bfs())
+            std::fprintf(stderr, "[jg msbfs] level %d top-down, sparse reverse exchange: %lld pairs (dense: %lld words)\n",
+                         level, (long long)pairs_all, (long long)mat[(size_t)P * P]);
+        return true;
+    }
+
+    // the peers' halo slots for every own row (fv: the staging vectors, rv: the receive buffers)
+    void reverse_exchange_dense(std::vector<void*>& fv, std::vector<void*>& rv) {
+        exchange_halo_reverse(g, JG_ADJ_BOTH, fv, rv, sizeof(unsigned long long), ncclUint64);
+        each([&](MsBfsShard& s) {
+            const int64_t nrecv = s.sh->halo_both.send_off[g.P];
+            if (nrecv > 0) {
+                msbfs_td_recv_kernel<<<grid_for(nrecv, kBlock, 256 * 8), kBlock, 0, s.sh->stream>>>(
+                    s.rbuf.get(), s.sh->halo_both.send_src.get(), nrecv, s.vis.get(), s.F[cur ^ 1].get(),
+                    s.touched.get(), s.touched_off.get(), s.ctr.get() + 1);
+                JG_LAUNCH_CHECK();
+            }
+        });
+    }
+
+    // A level pulled by every own row with entries (the merge engine or the exit kernels), then the scan
+    // of its output for the next level's direction.  have_live: live[0] holds this level's live bits
+    void pull_level(bool have_live) {
+        prev_td = false;
+        if (need_fwd) {  // stale halo segments: the lazy forward exchange
+            std::vector<void*> bufs;
+            for (auto& s : sv) bufs.push_back(s.F[cur].peer());
+            exchange_vec(g, sv[0].adj, bufs, sizeof(unsigned long long), ncclUint64);
+            need_fwd = false;
+        }
+        bool queued_next = false;  // this pull level built the next level's top-down queue
+        each([&](MsBfsShard& s) {
+            Shard& sh = *s.sh;
+            const PullPlan& plan = *s.plan;
+            // (with the top-down path the frontier count ends the traversal: no changed flag, whose
+            // one-word store every gaining row's wave would repeat)
+            if (!td_ok) JG_HIP(hipMemsetAsync(s.changed.get(), 0, sizeof(int32_t), sh.stream));
+            // rows without pull entries are not written by a pull level: a source among them keeps
+            // its level-0 word in this output vector unless cleared here, and the frontier scan would
+            // count it (one extra level)
+            if (td_ok && s.live_rows < sh.rows && !s.src_rows.empty()) {
+                msbfs_zero_tail_sources_kernel<<<1, kWave, 0, sh.stream>>>(
+                    s.F[cur ^ 1].get(), s.srcs.get(), (int)s.src_rows.size(), s.live_rows);
+                JG_LAUNCH_CHECK();
+            }
+            MsBfsOp op = make_op(s, level + 1);
+            op.nwl = level + 1 < kMsLevelWords ? s.nwl.get() + (int64_t)(level + 1) * sh.rows : nullptr;
+            op.changed = td_ok ? nullptr : s.changed.get();
+            // Live bits: the sources present in some word of this level's gathered vector.  A row
+            // none of whose unvisited bits is live gains nothing, so the light rows skip it
+            // (MsBfsOp::active) and the split skips every merge task whose rows are all such
+            // (their partials are then stale, and finalize's live mask discards them).  At
+            // RMAT-26 the last pull level has ~all rows done and the one before ~40% of band 0.
+            unsigned long long* lw = s.live.get();
+            if (!have_live) {
+                const int64_t vlen = g.vec_len(sh, s.adj);
+                JG_HIP(hipMemsetAsync(lw, 0, sizeof(unsigned long long), sh.stream));
+                msbfs_live_kernel<<<red_grid(vlen), kRedThreads, 0, sh.stream>>>(s.F[cur].get(), vlen, lw);
+                JG_LAUNCH_CHECK();
+            }
+            op.live = lw;
+            // msbfs_skip_first: no task bitmaps on the traversal's first pull level (few rows can be
+            // done there; every task runs, the finalize's live mask keeps it exact)
+            const bool no_bitmaps = pull_levels == 0;
+            // msbfs_exit 1: every row with entries exits early on pull levels where fewer than
+            // msbfs_exit_live permille of band 0's merge tasks hold a row that can still gain a bit
+            // (their live count is read back once); 2: on every pull level
+            const MsBu& bx = s.bx;
+            int64_t exit_rows = bx.rows > 0 && tune().msbfs_exit == 2 ? bx.rows : 0;
+            const bool exit_probe = bx.rows > 0 && tune().msbfs_exit == 1 && !no_bitmaps && !s.todo.empty();
+            std::vector<const uint32_t*> tl;
+            for (size_t b = 0; b < s.todo.size() && !no_bitmaps && !exit_rows; ++b) {
+                const SliceBand& bd = *plan.bands[b];
+                if (bd.tasks == 0 || bd.rows() == 0) {
+                    tl.push_back(nullptr);
+                    continue;
+                }
+                msbfs_todo_kernel<<<grid_for(bd.rows()), kBlock, 0, sh.stream>>>(
+                    s.vis.get(), bd.row_begin, bd.rows(), lw, s.todo[b].get());
+                JG_LAUNCH_CHECK();
+                // band 0 counts its live tasks apart (work[3]), and the count decides: an exit level
+                // builds no bitmaps for the other bands
+                const bool probe = exit_probe && b == 0;
+                if (probe) JG_HIP(hipMemsetAsync(s.work.get() + 3, 0, sizeof(unsigned long long), sh.stream));
+                msbfs_task_live_kernel<<<red_grid(bd.tasks), kRedThreads, 0, sh.stream>>>(
+                    bd.task_rows.get(), bd.tasks, s.todo[b].get(), s.tlive[b].get(), s.work.get() + (probe ? 3 : 0));
+                JG_LAUNCH_CHECK();
+                if (probe) {
+                    unsigned long long xlive = 0;
+                    copy_d2h(&xlive, s.work.get() + 3, sizeof xlive, sh.stream);
+                    const bool go = (double)xlive * 1000.0 < (double)s.exit_tasks * (double)tune().msbfs_exit_live;
+                    s.xlive_permille = s.exit_tasks ? (double)xlive * 1000.0 / (double)s.exit_tasks : 1000.0;
+                    if (debug_bfs())
+                        std::fprintf(stderr, "[jg msbfs] level %d band 0: %llu of %lld merge tasks live -> %s\n",
+                                     level, xlive, (long long)s.exit_tasks, go ? "early exit" : "merge");
+                    if (go) {
+                        exit_rows = bx.rows;
+                        break;
+                    }
+                    s.b0_live_merged += xlive;  // (work[0] holds the other bands' live tasks)
+                }
+                tl.push_back(reinterpret_cast<const uint32_t*>(s.tlive[b].get()));
+            }
+            if (no_bitmaps && &s == &sv.front()) ++unskipped_levels;
+            if (exit_rows) {  // every row with entries through the exit kernels, no merge launch
+                s.exit_level_tasks += (double)s.all_tasks;
+                if (no_bitmaps) s.exit_unskipped_tasks += (double)s.all_tasks;
+                unsigned long long before = 0, after = 0;
+                if (debug_bfs()) copy_d2h(&before, bx.examined, sizeof before, sh.stream);
+                const unsigned xg = red_grid((bx.rows + 63) / 64 * kWave);
+                msbfs_exit_first_kernel<<<xg, kRedThreads, 0, sh.stream>>>(bx, op, s.xrest.get());
+                JG_LAUNCH_CHECK();
+                msbfs_exit_rest_kernel<<<xg, kRedThreads, 0, sh.stream>>>(bx, op, s.xrest.get());
+                JG_LAUNCH_CHECK();
+                ++s.exit_all_levels;
+                if (debug_bfs()) {
+                    copy_d2h(&after, bx.examined, sizeof after, sh.stream);
+                    std::fprintf(stderr, "[jg msbfs] level %d exit rows [0, %lld): %llu entries examined\n",
+                                 level, (long long)bx.rows, after - before);
+                }
+            } else {
+                // rows without pull entries are not finalised: they gain nothing, their words are zero
+                // on every output vector, and their new-bit words are masked at output
+                // (msbfs_levels_to_planes_kernel)
+                launch_pull(*s.c.pull, plan, op, s.hub.get(), sh.stream, ctx.profiling ? &ctx : nullptr, &sh,
+                            s.split.size() ? s.split.get() : (unsigned long long*)nullptr, true,
+                            tl.empty() ? nullptr : tl.data());
+            }
+            if (td_ok) {  // the next level's frontier counter (its direction) and, on one shard, live bits
+                zero_words({{s.ctr.get(), sizeof(unsigned long long)}, {lw, sizeof(unsigned long long)}}, sh.stream);
+                // a level whose exit bands had (almost) no live task leaves a small frontier, which
+                // the next level pushes top-down: its queue is built here, in the same pass
+                const bool qnext = td_one && !s.todo.empty() && s.xlive_permille < (double)tune().msbfs_scan_queue;
+                s.xlive_permille = 1000.0;
+                // rows without pull entries gained nothing (a pull level does not finalise them):
+                // the scans stop at the empty suffix (RMAT-26 BOTH: 34 M of 67 M rows)
+                const int64_t ne = s.live_rows;
+                if (qnext) {
+                    msbfs_frontier_live_kernel<<<grid_for((ne + 3) / 4), kBlock, 0, sh.stream>>>(
+                        s.F[cur ^ 1].get(), ne, s.c.push->row_ptr.get(), s.queue[qc ^ 1].get(),
+                        s.qoff[qc ^ 1].get(), s.ctr.get(), lw);
+                    queued_next = true;
+                } else {
+                    msbfs_scan_kernel<<<red_grid(ne), kRedThreads, 0, sh.stream>>>(
+                        s.F[cur ^ 1].get(), ne, s.c.push->row_ptr.get(), lw, s.ctr.get());
+                }
+                JG_LAUNCH_CHECK();
+            }
+        });
+        if (td_ok) {
+            read_frontier();
+            combine_live();
+            live_ready = true;
+            if (queued_next) {  // the queue is in slot qc ^ 1 (one shard): the next top-down level's
+                qc ^= 1;
+                queued = true;
+            }
+        }
+        ++pull_levels;
+        need_fwd = g.P > 1;
+    }
+
+    Graph& g;
+    Ctx& ctx;
+    Shard& sh0;
+    const int direction, ns;
+    const unsigned long long full;  // a bit per source of the batch
+    std::vector<MsBfsShard> sv;     // per local shard
+    std::vector<int64_t> src_local;
+    std::vector<int> src_shard;
+    bool td_one = false, td_shard = false, td_ok = false;  // top-down levels: one shard / sharded / either
+    int64_t push_nnz = 0;  // entries of the push adjacency, all shards and ranks (the direction rule)
+    // need_fwd: the current F's halo segments are stale.  The forward exchange runs lazily, before a
+    // pull level: a top-down level reads own frontier words only (and writes own rows only)
+    bool need_fwd = false;
+    int cur = 0, level = 0, qc = 0;
+    int64_t g_nq = 0, g_mf = 0;  // the current frontier's vertices and push entries, all shards and ranks
+    // levels whose depths are nwl words (bit L): a pull level finalises every own row (its word is
+    // written, zero or not); a top-down level records (row, word) pairs of the rows it reached
+    unsigned word_levels = 0;
+    // queued: sv[i].queue[qc] holds the current frontier; live_ready: live[0] holds its live bits
+    // (both from the previous level's end)
+    bool queued = false, live_ready = false;
+    bool prev_td = false;  // the previous level ran top-down: F[cur ^ 1]'s nonzero own words are
+                           // exactly its input queue (sv[i].queue[qc ^ 1][0, nq_in))
+    // work of the levels (jg_stats.algorithmic_bytes): pull levels (per shard: the live merge tasks
+    // counted on the device, or every task when the skip is off) and top-down frontier entries
+    int pull_levels = 0;
+    int unskipped_levels = 0;  // pull levels that ran every merge task (msbfs_skip_first)
+    double td_entries = 0, td_touched = 0, td_queued = 0;
+    double td_row_passes = 0;  // rows the row-order applies read (8 B each)
+};
+
+// bit-parallel BFS in batches of 64 sources; works sharded
+void bfs_batches(Graph& g, const int64_t* source_vids, int nsrc, int direction, int max_depth,
+                 int32_t* const* depth_rows, bool keep, Event& t0, Event& t1) {
+    Ctx& ctx = *g.ctx;
+    float total_ms = 0;
+    int max_levels = 0;
+    double work_bytes = 0, work_entries = 0;
+    for (int b0 = 0; b0 < nsrc; b0 += 64) {
+        MsBfsBatch batch(g, direction, source_vids + b0, std::min(64, nsrc - b0));
+        const int levels = batch.run(max_depth, t0, t1);
+        JG_HIP(hipEventSynchronize(t1));
+        float ms = 0;
+        JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+        total_ms += ms;
+        max_levels = std::max(max_levels, levels);
+        batch.add_work(work_bytes, work_entries);
+        batch.deliver(depth_rows ? depth_rows + b0 : nullptr, keep);
+    }
+    if (keep) g.kept_nsrc = nsrc;
+    ctx.last.compute_ms = total_ms;
+    ctx.last.levels = max_levels;
+    ctx.last.supersteps = max_levels;
+    ctx.last.algorithmic_bytes = work_bytes;
+    ctx.last.edges_traversed = work_entries;  // adjacency entries the levels examined
+}
+}  // namespace
+
 void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int max_depth, int32_t* const* depth_rows,
              bool keep) {
     if (nsrc <= 0) fail(JG_ERR_ARG, "nsrc must be positive");
@@ -3036,955 +4004,17 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
                             g.shards[0]->halo_both.on && tune().sharded_bfs;
     Shard& sh0 = *g.shards[0];
     DeviceGuard dg0(sh0.device);
-    Event t0, t1;
-    if (sharded_do) {
-        int shard = -1;
-        const int64_t l = local_of_vid(g, source_vids[0], &shard);
-        double edges = 0;
-        float ms = 0;
-        const int levels = dobfs_sharded(g, l >= 0 ? shard : -1, l, max_depth, &edges, &ms);
-        ctx.last.compute_ms = ms;
-        ctx.last.levels = levels;
-        ctx.last.supersteps = levels;
-        ctx.last.edges_traversed = l >= 0 ? edges / 2 : 0;
-        if (depth_rows && depth_rows[0])
-            for (auto& sp : g.shards) rows_to_dense(g, *sp, sp->bfs_depth.peer(), depth_rows[0]);
-        if (keep) keep_depth_rows(g);
-        prof_collect(ctx, g);
-    } else if (single) {
-        Shard& sh = sh0;
-        const BfsCsrs c = pick_csrs(sh, direction);
-        int shard = 0;
-        const int64_t l = local_of_vid(g, source_vids[0], &shard);
-        if (sh.bfs_depth.size() != (size_t)std::max<int64_t>(sh.rows, 1)) {
-            sh.bfs_depth.alloc(std::max<int64_t>(sh.rows, 1));
-            sh.bfs_depth_tail_clean = false;
-        }
-        DevBuf<int32_t>& depth = sh.bfs_depth;
-        int levels = 0;
-        double edges = 0;
-        if (l < 0) {
-            fill_i32_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(depth.get(), sh.rows, -1);
-            JG_LAUNCH_CHECK();
-            sh.bfs_depth_tail_clean = true;
-            JG_HIP(hipEventRecord(t0, sh.stream));
-            JG_HIP(hipEventRecord(t1, sh.stream));
-        } else {
-            bfs_buffers(sh);
-            if (c.pull) bfs_first_col(sh, *c.pull);
-            // BOTH: rows of the empty suffix (no entry) are never reached, so their depths stay -1 from one
-            // traversal to the next and the init skips them, whatever the caller wants back (the
-            // depth output and kept rows no longer pay a longer init than want=False).  The suffix is filled
-            // once, before t0; a source inside it (an isolated vertex) takes the full init and leaves its 0
-            // behind, so the next traversal refills.
-            const int64_t live = c.push == c.pull && c.pull->empty_from >= 0 ? std::min(sh.rows, c.pull->empty_from)
-                                                                              : sh.rows;
-            if (live < sh.rows && !sh.bfs_depth_tail_clean) {
-                fill_i32_kernel<<<grid_for(sh.rows - live), kBlock, 0, sh.stream>>>(depth.get() + live, sh.rows - live, -1);
-                JG_LAUNCH_CHECK();
-            }
-            const bool full_init = l >= live;
-            region_mark(sh.stream, true);
-            JG_HIP(hipEventRecord(t0, sh.stream));
-            levels = dobfs_single(ctx, sh, c, l, max_depth, depth.get(), &edges, nullptr, t1, full_init);
-            sh.bfs_depth_tail_clean = !full_init || live == sh.rows;
-        }
-        JG_HIP(hipEventSynchronize(t1));
-        float ms = 0;
-        JG_HIP(hipEventElapsedTime(&ms, t0, t1));
-        ctx.last.compute_ms = ms;
-        ctx.last.levels = levels;
-        ctx.last.supersteps = levels;
-        ctx.last.edges_traversed = direction == JG_DIR_BOTH ? edges / 2 : edges;
-        const Csr* degcsr = c.push ? c.push : c.pull;
-        ctx.last.algorithmic_bytes = 4.0 * (double)degcsr->nnz + 12.0 * (double)sh.rows;
-        if (depth_rows && depth_rows[0]) rows_to_dense(g, sh, depth.get(), depth_rows[0]);
-        if (keep) keep_depth_rows(g);
-        prof_collect(ctx, g);
-    } else if (nsrc <= kNarrowMax && g.P == 1 && g.shards.size() == 1 && tune().bfs_narrow &&
-               pick_csrs(sh0, direction).push && pick_csrs(sh0, direction).pull) {
-        // 2..8 sources on one shard: the narrow engine (jg_narrow.hip), one frontier byte per row
-        Shard& sh = sh0;
-        const BfsCsrs c = pick_csrs(sh, direction);
-        std::vector<int64_t> loc((size_t)nsrc);
-        std::vector<int> shard((size_t)nsrc);
-        locals_of_vids(g, source_vids, nsrc, loc.data(), shard.data());
-        DevBuf<int32_t> planes;
-        if (depth_rows || keep) planes.alloc(std::max<int64_t>((int64_t)nsrc * sh.rows, 1));
-        const NarrowRun r = narrow_bfs(ctx, sh, *c.push, *c.pull, loc.data(), nsrc, max_depth,
-                                       planes.size() ? planes.get() : nullptr);
-        ctx.last.compute_ms = r.ms;
-        ctx.last.levels = r.levels;
-        ctx.last.supersteps = r.levels;
-        ctx.last.edges_traversed = r.entries;
-        ctx.last.algorithmic_bytes = r.bytes;
-        if (depth_rows)
-            for (int s = 0; s < nsrc; ++s)
-                if (depth_rows[s]) rows_to_dense(g, sh, planes.get() + (size_t)s * sh.rows, depth_rows[s]);
-        if (keep) {
-            sh.kept_depth.swap(planes);
-            g.kept_nsrc = nsrc;
-        }
-        prof_collect(ctx, g);
-    } else {
-        // bit-parallel BFS in batches of 64 sources; works sharded (frontier words allgathered)
-        float total_ms = 0;
-        int max_levels = 0;
-        double work_bytes = 0, work_entries = 0;
-        for (int b0 = 0; b0 < nsrc; b0 += 64) {
-            const int ns = std::min(64, nsrc - b0);
-            const unsigned long long full = ns == 64 ? ~0ull : ((1ull << ns) - 1ull);
-            struct St {
-                DevBuf<unsigned long long> F[2], vis;
-                DevBuf<int32_t> depth, changed;  // depth: int32 planes once widened
-                DevBuf<uint8_t> depth8;           // byte planes of levels kMsLevelWords .. 254 (allocated on reaching them)
-                DevBuf<unsigned long long> nwl;   // [kMsLevelWords][rows] new-bit words of levels 0 .. kMsLevelWords-1
-                DevBuf<unsigned long long> hub, split;
-                DevBuf<unsigned long long> live;  // [0] the pull level's live bits, [1] all sources (top-down)
-                DevBuf<unsigned long long> xrest;  // msbfs_exit: the rows pass B scans (a bit per row)
-                MsBu bx{};                         // msbfs_exit: every row with entries (bx.rows 0: off on this shard)
-                int64_t exit_tasks = 0;            // band 0's merge tasks (its live count decides an exit level)
-                int64_t all_rows = 0;   // the rows a pull level finalises (those with entries)
-                int exit_all_levels = 0;
-                // merge tasks of the bands the exit kernels took instead (on levels that count every task, and on all)
-                double exit_unskipped_tasks = 0, exit_level_tasks = 0;
-                unsigned long long b0_live_merged = 0;     // msbfs_exit 1: band 0's live tasks of levels that merged it
-                double xlive_permille = 1000.0;            // the last probe's live share of band 0's tasks
-                std::vector<DevBuf<unsigned long long>> todo, tlive;  // per band: row and task bitmaps
-                DevBuf<int64_t> dloc;             // [64] each source's own row (-1: another shard's)
-                // levels recorded as (row, new word) records instead of nwl words (level 0 from the sources and
-                // every top-down level below kMsLevelWords): {level, count, rows, words}
-                struct Rec {
-                    int level = 0;
-                    int64_t n = 0;
-                    DevBuf<int32_t> rows;
-                    DevBuf<unsigned long long> words;
-                };
-                std::vector<Rec> recs;
-                DevBuf<unsigned long long> work;  // [0] live merge tasks over all pull levels, [1] reached pairs,
-                                                  // [2] entries the early-exit bottom-up levels scanned,
-                                                  // [3] band 0's live tasks of this level (msbfs_exit 1)
-                int64_t light_nnz = 0, all_tasks = 0;  // entries outside the split, merge tasks of all bands
-            };
-            std::vector<St> st(g.shards.size());
-            const BfsCsrs c0 = pick_csrs(sh0, direction);
-            const uint32_t adj0 = adj_of(sh0, c0);
-            // Levels whose frontier has few edges run top-down: on one shard with a push adjacency, and
-            // on a sharded BOTH traversal over the halo plan (msbfs_td 1; 2 = one shard only).  Sharded,
-            // a shard pushes its own frontier rows; bits for a peer's vertex collect in its halo slot and
-            // go to the owner by the reverse halo exchange (msbfs_td_recv_kernel).
-            const bool td_one = g.shards.size() == 1 && g.P == 1 && c0.push != nullptr && tune().msbfs_td != 0;
-            const bool td_shard = g.P > 1 && g.P <= kMaxPeersMs && direction == JG_DIR_BOTH && sh0.halo_both.on &&
-                                  tune().msbfs_td == 1;
-            const bool td_ok = td_one || td_shard;
-            struct Td {
-                DevBuf<int32_t> queue[2], touched;
-                DevBuf<int64_t> qoff[2], touched_off;
-                DevBuf<unsigned long long> ctr;   // [0] frontier, [1] touched, [2] halo slots set
-                DevBuf<int64_t> srcs;             // the shard's distinct source rows
-                DevBuf<unsigned long long> rbuf;  // sharded: the peers' halo slots for own rows (send-list order)
-                DevBuf<unsigned long long> hs;    // sharded: halo staging (compact positions), zero between levels
-                DevBuf<int32_t> hlist;            // sharded: the staging slots a level set
-                DevBuf<int64_t> hlist_off;        // appender scratch
-                DevBuf<unsigned int> bcount;      // [kRedBlocks][P] set staging slots per histogram block and peer
-                DevBuf<unsigned long long> pairs, rpairs, pcnt;  // sparse reverse exchange: sent / received
-                                                                 // (offset, word) pairs, per-peer counts + cursors
-                std::vector<int64_t> src_rows;
-                int64_t nq = 0, mf = 0;
-                int64_t nrp = 0;                  // pairs received by the last sparse exchange
-                PairRuns pv{};                    // their per-peer runs and this shard's send-list offsets
-                int64_t nq_in = 0;                // the last top-down level's input frontier (its queue)
-                bool rowapply = false;            // this level's apply passes over every row (no touched list)
-            };
-            std::vector<Td> tds(g.shards.size());
-            std::vector<int64_t> src_local((size_t)ns);
-            std::vector<int> src_shard((size_t)ns);
-            locals_of_vids(g, source_vids + b0, ns, src_local.data(), src_shard.data());
-            int64_t push_nnz = 0;  // entries of the push adjacency, all shards and ranks (the direction rule)
-            for (size_t i = 0; i < g.shards.size(); ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                const BfsCsrs c = pick_csrs(sh, direction);
-                if (!c.pull) fail(JG_ERR_UNSUPPORTED, "multi-source BFS needs the pull adjacency");
-                const PullPlan& plan = (c.pull == &sh.both) ? sh.plan_both : sh.plan_in;
-                if (c.pull == &sh.out) fail(JG_ERR_UNSUPPORTED, "multi-source IN traversal is not supported");
-                if (c.push) push_nnz += c.push->nnz;
-                St& t = st[i];
-                const int64_t len = g.vec_len(sh, adj_of(sh, c));
-                t.F[0].alloc(len);
-                t.F[1].alloc(len);
-                t.vis.alloc(std::max<int64_t>(sh.rows, 1));
-                t.nwl.alloc(std::max<int64_t>(sh.rows * kMsLevelWords, 1));
-                t.changed.alloc(1);
-                t.hub.alloc(std::max<int64_t>(plan.num_chunks, 1));
-                if (tune().msbfs_split && plan.split_rows > 0) t.split.alloc(plan.split_partial_len());
-                t.live.alloc(3);  // [2]: a split level's pull live bits
-                t.work.alloc(4);
-                JG_HIP(hipMemsetAsync(t.work.get(), 0, 4 * sizeof(unsigned long long), sh.stream));
-                if (tune().msbfs_exit > 0 && t.split.size() && !plan.bands.empty())
-                    t.xrest.alloc(std::max<int64_t>((sh.rows + 63) / 64, 1));
-                t.light_nnz = c.pull->nnz;
-                if (t.split.size() && plan.split_rows > 0) {
-                    int64_t split_nnz = 0;
-                    copy_d2h(&split_nnz, c.pull->row_ptr.get() + plan.split_rows, sizeof split_nnz, sh.stream);
-                    t.light_nnz -= split_nnz;
-                    for (const auto& bd : plan.bands) t.all_tasks += bd->tasks;
-                }
-                const unsigned long long lw[2] = {full, full};
-                copy_h2d(t.live.get(), lw, sizeof lw, sh.stream);
-                if (t.split.size() && tune().msbfs_skip) {
-                    t.todo.resize(plan.bands.size());
-                    t.tlive.resize(plan.bands.size());
-                    for (size_t b = 0; b < plan.bands.size(); ++b) {
-                        t.todo[b].alloc(std::max<int64_t>((plan.bands[b]->rows() + 63) / 64, 1));
-                        t.tlive[b].alloc(std::max<int64_t>((plan.bands[b]->tasks + 63) / 64, 1));
-                    }
-                }
-                std::vector<int64_t> loc(ns, -1);
-                for (int s = 0; s < ns; ++s)
-                    if (src_local[(size_t)s] >= 0 && src_shard[(size_t)s] == sh.index) loc[s] = src_local[(size_t)s];
-                // the shard's distinct source rows: its first top-down queue (msbfs_source_queue_kernel)
-                for (int64_t l : loc)
-                    if (l >= 0 && std::find(tds[i].src_rows.begin(), tds[i].src_rows.end(), l) == tds[i].src_rows.end())
-                        tds[i].src_rows.push_back(l);
-                t.dloc.alloc(ns);
-                copy_h2d(t.dloc.get(), loc.data(), ns * sizeof(int64_t), sh.stream);
-                JG_HIP(hipStreamSynchronize(sh.stream));
-            }
-            allreduce_sum_i64(g, &push_nnz, 1);
-            // need_fwd: the current F's halo segments are stale.  The forward exchange runs lazily, before a
-            // pull level: a top-down level reads own frontier words only (and writes own rows only)
-            bool need_fwd = g.P > 1;
-            int cur = 0, level = 0, qc = 0;
-            int64_t g_nq = 0, g_mf = 0;  // the current frontier's vertices and push entries, all shards and ranks
-            // touched (nullable): += the rows the top-down level just applied (its touched counter)
-            auto read_frontier = [&](double* touched = nullptr) {
-                int64_t v[2] = {0, 0};
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    DeviceGuard dg(sh);
-                    unsigned long long hh[2] = {0, 0};
-                    copy_d2h(hh, tds[i].ctr.get(), (touched ? 2 : 1) * sizeof(unsigned long long), sh.stream);
-                    const unsigned long long h = hh[0];
-                    if (touched) *touched += (double)(hh[1] >> kPackShift);
-                    tds[i].nq = (int64_t)(h >> kPackShift);
-                    tds[i].mf = (int64_t)(h & kEdgeMask);
-                    v[0] += tds[i].nq;
-                    v[1] += tds[i].mf;
-                }
-                allreduce_sum_i64(g, v, 2);
-                g_nq = v[0];
-                g_mf = v[1];
-            };
-            // live bits of the next pull level from every shard's own rows (the top-down apply or the scan
-            // after a pull level ORed them into live[0]): OR over the local shards and the ranks, a superset
-            // of what the shard's gathered vector holds, which is all the task skip needs
-            auto combine_live = [&]() {
-                if (g.shards.size() == 1 && ctx.nranks == 1) return;
-                uint64_t v = 0;
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    DeviceGuard dg(sh);
-                    uint64_t w = 0;
-                    copy_d2h(&w, st[i].live.get(), sizeof w, sh.stream);
-                    v |= w;
-                }
-                v = allreduce_or_u64(g, v);
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    DeviceGuard dg(sh);
-                    copy_h2d(st[i].live.get(), &v, sizeof v, sh.stream);
-                }
-            };
-            auto build_frontier = [&](int qslot) {
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    DeviceGuard dg(sh);
-                    const BfsCsrs c = pick_csrs(sh, direction);
-                    const int64_t ne = pull_live_rows(sh, c);
-                    JG_HIP(hipMemsetAsync(tds[i].ctr.get(), 0, sizeof(unsigned long long), sh.stream));
-                    msbfs_frontier_kernel<<<grid_for(ne), kBlock, 0, sh.stream>>>(
-                        st[i].F[cur].get(), ne, c.push->row_ptr.get(), tds[i].queue[qslot].get(),
-                        tds[i].qoff[qslot].get(), tds[i].ctr.get());
-                    JG_LAUNCH_CHECK();
-                }
-                read_frontier();
-            };
-            if (td_ok) {  // allocated before the timed region (~2.3 GB at RMAT-26 on one shard)
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    DeviceGuard dg(sh);
-                    Td& td = tds[i];
-                    const size_t r1 = (size_t)std::max<int64_t>(sh.rows, 1);
-                    for (int k = 0; k < 2; ++k) {
-                        td.queue[k].alloc(r1);
-                        td.qoff[k].alloc(r1);
-                    }
-                    td.touched.alloc(r1);
-                    td.touched_off.alloc(r1);
-                    td.ctr.alloc(3);
-                    td.srcs.alloc(std::max<size_t>(td.src_rows.size(), 1));
-                    if (!td.src_rows.empty())
-                        copy_h2d(td.srcs.get(), td.src_rows.data(), td.src_rows.size() * sizeof(int64_t), sh.stream);
-                    if (td_shard) {
-                        const Halo& h = sh.halo_both;
-                        td.rbuf.alloc(std::max<int64_t>(h.send_off[g.P], 1));
-                        td.hs.alloc(g.vec_len(sh, JG_ADJ_BOTH));
-                        td.hlist.alloc(std::max<int64_t>(h.recv_off[g.P], 1));
-                        td.hlist_off.alloc(std::max<int64_t>(h.recv_off[g.P], 1));
-                        if (tune().msbfs_sparse) {
-                            td.pairs.alloc(2 * std::max<int64_t>(h.recv_off[g.P], 1));
-                            td.rpairs.alloc(2 * std::max<int64_t>(h.send_off[g.P], 1));
-                            td.pcnt.alloc(2 * (size_t)g.P);
-                            td.bcount.alloc((size_t)kRedBlocks * g.P);
-                        }
-                    }
-                }
-            }
-            for (size_t i = 0; i < g.shards.size(); ++i) {  // the early exit's first columns (before t0)
-                Shard& sh = *g.shards[i];
-                const BfsCsrs c = pick_csrs(sh, direction);
-                if (c.pull) bfs_first_col(sh, *c.pull);
-            }
-            prof_discard_exchanges(g);  // exchange pairs never straddle t0
-            region_mark(sh0.stream, true);
-            JG_HIP(hipEventRecord(t0, sh0.stream));
-            // the call's state, inside the timed region: frontiers, visited bits, the halo staging, the
-            // sources (and level 0's depth record)
-            for (size_t i = 0; i < g.shards.size(); ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                St& t = st[i];
-                const BfsCsrs c = pick_csrs(sh, direction);
-                if (td_one && c.pull == c.push) {
-                    // one shard, BOTH: only rows before the empty suffix are read after level 0 (no gather,
-                    // push target, scan, apply or finalise reaches the rows past it, §5; a directed traversal
-                    // gathers columns without pull entries of their own, so it clears everything); the source
-                    // rows among them get their words stored by the init below.  RMAT-26 BOTH: 34 of 67 M rows,
-                    // three 537 MB clears halved
-                    const int64_t ne = pull_live_rows(sh, c), base = g.vec_pos(sh, adj_of(sh, c)).base;
-                    if (std::getenv("JG_MSBFS_POISON") && ne < sh.rows) {  // (test switch: garbage past the suffix)
-                        const size_t tail = (size_t)(sh.rows - ne) * sizeof(unsigned long long);
-                        JG_HIP(hipMemsetAsync(t.F[0].get() + base + ne, 0xA5, tail, sh.stream));
-                        JG_HIP(hipMemsetAsync(t.F[1].get() + base + ne, 0x5A, tail, sh.stream));
-                        JG_HIP(hipMemsetAsync(t.vis.get() + ne, 0xC3, tail, sh.stream));
-                    }
-                    JG_HIP(hipMemsetAsync(t.F[0].get() + base, 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
-                    JG_HIP(hipMemsetAsync(t.F[1].get() + base, 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
-                    JG_HIP(hipMemsetAsync(t.vis.get(), 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
-                } else {
-                    zero_gathered(g, sh, adj_of(sh, c), t.F[0].get(), sizeof(unsigned long long));
-                    zero_gathered(g, sh, adj_of(sh, c), t.F[1].get(), sizeof(unsigned long long));
-                    JG_HIP(hipMemsetAsync(t.vis.get(), 0, t.vis.bytes(), sh.stream));
-                }
-                if (tds[i].hs.size()) zero_gathered(g, sh, JG_ADJ_BOTH, tds[i].hs.get(), sizeof(unsigned long long));
-                St::Rec* r0 = nullptr;
-                if (td_ok) {  // level 0 as records of the source rows
-                    t.recs.emplace_back();
-                    r0 = &t.recs.back();
-                    r0->level = 0;
-                    r0->n = ns;
-                    r0->rows.alloc(ns);
-                    r0->words.alloc(ns);
-                } else {  // level 0's words
-                    JG_HIP(hipMemsetAsync(t.nwl.get(), 0, (size_t)sh.rows * sizeof(unsigned long long), sh.stream));
-                }
-                msbfs_init_kernel<<<1, kWave, 0, sh.stream>>>(t.dloc.get(), ns, t.F[0].get(), t.vis.get(),
-                                                          r0 ? nullptr : t.nwl.get(), sh.rows, g.vec_pos(sh, adj_of(sh, c)),
-                                                          r0 ? r0->rows.get() : nullptr, r0 ? r0->words.get() : nullptr);
-                JG_LAUNCH_CHECK();
-            }
-            if (!td_ok) {
-                std::vector<void*> bufs;
-                for (auto& t : st) bufs.push_back(t.F[0].peer());
-                exchange_vec(g, adj0, bufs, sizeof(unsigned long long), ncclUint64);
-                need_fwd = false;
-            }
-            if (td_ok) {  // the level-0 frontier is the source rows: queued directly, no scan of F
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    DeviceGuard dg(sh);
-                    const BfsCsrs c = pick_csrs(sh, direction);
-                    msbfs_source_queue_kernel<<<1, kWave, 0, sh.stream>>>(tds[i].srcs.get(), (int)tds[i].src_rows.size(),
-                                                                       c.push->row_ptr.get(), tds[i].queue[0].get(),
-                                                                       tds[i].qoff[0].get(), tds[i].ctr.get());
-                    JG_LAUNCH_CHECK();
-                }
-                read_frontier();
-            }
-            // queued: tds[i].queue[qc] holds the current frontier; live_ready: live[0] holds its live bits
-            // (both from the previous level's end)
-            // Depths: levels 0 .. kMsLevelWords-1 as new-bit words (nwl), levels up to 254 as byte planes
-            // (allocated, all 255 = unreached, when the traversal reaches them), beyond as int32 planes (a
-            // traversal about to write level 255 widens the byte planes first)
-            auto ensure_depth8 = [&]() {
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
-                    if (t.depth8.size() || t.depth.size()) continue;
-                    DeviceGuard dg(sh);
-                    t.depth8.alloc(std::max<int64_t>(sh.rows * ns, 1));
-                    JG_HIP(hipMemsetAsync(t.depth8.get(), 0xFF, t.depth8.bytes(), sh.stream));
-                }
-            };
-            auto widen = [&]() {
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
-                    if (t.depth.size()) continue;
-                    DeviceGuard dg(sh);
-                    const int64_t total = std::max<int64_t>(sh.rows * ns, 1);
-                    t.depth.alloc(total);
-                    if (t.depth8.size()) {
-                        msbfs_widen_kernel<<<grid_for(total), kBlock, 0, sh.stream>>>(t.depth8.get(), total, t.depth.get());
-                        JG_LAUNCH_CHECK();
-                    } else {
-                        fill_i32_kernel<<<grid_for(total), kBlock, 0, sh.stream>>>(t.depth.get(), total, -1);
-                        JG_LAUNCH_CHECK();
-                    }
-                    JG_HIP(hipStreamSynchronize(sh.stream));
-                    t.depth8.reset();
-                }
-            };
-            // levels whose depths are nwl words (bit L): a pull level finalises every own row (its word is
-            // written, zero or not); a top-down level records (row, word) pairs of the rows it reached
-            unsigned word_levels = td_ok ? 0u : 1u;
-            // the caller's int32 planes: the widened byte / int32 planes, then the word-recorded levels
-            auto materialize = [&](int levels_run) {
-                widen();
-                for (size_t i = 0; i < g.shards.size(); ++i) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
-                    DeviceGuard dg(sh);
-                    const int lw = std::min(levels_run + 1, kMsLevelWords);
-                    if (sh.rows > 0) {
-                        const Csr* pc = pick_csrs(sh, direction).pull;
-                        const int64_t ne = pc->empty_from >= 0 ? std::min(pc->empty_from, sh.rows) : sh.rows;
-                        msbfs_levels_to_planes_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(
-                            t.nwl.get(), lw, word_levels, sh.rows, ne, ns, t.depth.get());
-                        JG_LAUNCH_CHECK();
-                    }
-                    for (const auto& r : t.recs)
-                        if (r.n > 0 && r.level < lw) {
-                            msbfs_records_to_planes_kernel<<<grid_for(r.n), kBlock, 0, sh.stream>>>(
-                                r.rows.get(), r.words.get(), r.n, r.level, sh.rows, ns, t.depth.get());
-                            JG_LAUNCH_CHECK();
-                        }
-                    JG_HIP(hipStreamSynchronize(sh.stream));
-                }
-            };
-            // msbfs_exit: every row with entries scans its row with early exit (msbfs_exit_first_kernel /
-            // msbfs_exit_rest_kernel) on pull levels where few of band 0's merge tasks are live, and such a
-            // level runs no merge launch at all.  On the level after the frontier's peak a hub row finds all
-            // its unvisited live bits within its first entries: RMAT-22, band 0 examines 0.1% instead of
-            // 27.3% of the entries (tools/msbfs_exit_sim.py).  Band 0's live tasks alone decide
-            // (every exit band's bitmaps took the same decisions, round 4); each shard decides for its own
-            // rows.  (Only the exit bands through the exit, the light rows merged: RMAT-26 11.42 vs 11.20 ms.)
-            for (size_t i = 0; i < g.shards.size(); ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                const BfsCsrs c = pick_csrs(sh, direction);
-                const PullPlan& plan = (c.pull == &sh.both) ? sh.plan_both : sh.plan_in;
-                St& t = st[i];
-                if (tune().msbfs_exit > 0 && tune().pull_split && plan.split_rows > 0 && !plan.bands.empty() &&
-                    t.xrest.size() > 0 && plan.bands[0]->row_begin == 0 && plan.bands[0]->row_end > 0) {
-                    t.bx.rp = c.pull->row_ptr.get();
-                    t.bx.col = c.pull->col.get();
-                    t.bx.first_col = bfs_first_col(sh, *c.pull);
-                    t.all_rows = c.pull->empty_from >= 0 ? std::min(c.pull->empty_from, sh.rows) : sh.rows;
-                    t.bx.rows = t.all_rows;
-                    t.bx.examined = t.work.get() + 2;
-                    t.bx.first = tune().msbfs_exit_first;
-                    t.exit_tasks = plan.bands[0]->tasks;
-                }
-            }
-            bool queued = td_ok, live_ready = false;
-            bool prev_td = false;  // the previous level ran top-down: F[cur ^ 1]'s nonzero own words are
-                                   // exactly its input queue (tds[i].queue[qc ^ 1][0, nq_in))
-            // work of the levels (jg_stats.algorithmic_bytes): pull levels (per shard: the live merge tasks
-            // counted on the device, or every task when the skip is off) and top-down frontier entries
-            int pull_levels = 0;
-            int unskipped_levels = 0;  // pull levels that ran every merge task (msbfs_skip_first)
-            double td_entries = 0, td_touched = 0, td_queued = 0;
-            double td_row_passes = 0;  // rows the row-order applies read (8 B each)
-            while (max_depth < 0 || level < max_depth) {
-                if (level + 1 >= kMsLevelWords) ensure_depth8();
-                if (level + 1 >= 255) widen();
-                const bool td_level = td_ok && (double)g_mf < (double)push_nnz / (double)tune().bfs_alpha;
-                // a pull level (merge engine or the exit kernels) finalises every own row: its words need no clearing
-                if (!td_level && level + 1 < kMsLevelWords) word_levels |= 1u << (level + 1);
-                if (td_level && !queued) {
-                    build_frontier(qc ^ 1);
-                    qc ^= 1;
-                }
-                const bool have_live = live_ready;
-                queued = live_ready = false;
-                bool queued_next = false;  // this pull level built the next level's top-down queue
-                if (td_level) {
-                    std::vector<void*> fv, rv;
-                    for (size_t i = 0; i < g.shards.size(); ++i) {
-                        Shard& sh = *g.shards[i];
-                        DeviceGuard dg(sh);
-                        const BfsCsrs c = pick_csrs(sh, direction);
-                        St& t = st[i];
-                        Td& td = tds[i];
-                        // changed, the frontier / touched / staging counters, the live bits the apply ORs and the
-                        // sparse exchange's per-peer counts and cursors
-                        zero_words({{t.changed.get(), sizeof(int32_t)},
-                                    {td.ctr.get(), 3 * sizeof(unsigned long long)},
-                                    {t.live.get(), sizeof(unsigned long long)},
-                                    {td.pcnt.get(), td.pcnt.bytes()}},
-                                   sh.stream);
-                        // the output's own words start at zero (the first toucher of a word queues it): after a
-                        // top-down level only its input queue's words are set, otherwise clear every own row
-                        if (prev_td) {
-                            if (td.nq_in > 0) {
-                                msbfs_zero_list_kernel<<<grid_for(td.nq_in), kBlock, 0, sh.stream>>>(
-                                    t.F[cur ^ 1].get(), td.queue[qc ^ 1].get(), td.nq_in);
-                                JG_LAUNCH_CHECK();
-                            }
-                        } else if (level > 0) {  // level 0: F[1] is as the init zeroed it
-                            // rows without pull entries are never written after level 0: their words are zero
-                            // except an isolated source's level-0 word, cleared apart (RMAT-26: 215 of 537 MB
-                            // cleared)
-                            const int64_t ne = c.pull && c.pull->empty_from >= 0 ? std::min(c.pull->empty_from, sh.rows)
-                                                                                 : sh.rows;
-                            JG_HIP(hipMemsetAsync(t.F[cur ^ 1].get(), 0, (size_t)ne * sizeof(unsigned long long), sh.stream));
-                            if (ne < sh.rows && !td.src_rows.empty()) {
-                                msbfs_zero_tail_sources_kernel<<<1, kWave, 0, sh.stream>>>(
-                                    t.F[cur ^ 1].get(), td.srcs.get(), (int)td.src_rows.size(), ne);
-                                JG_LAUNCH_CHECK();
-                            }
-                        }
-                        td.nq_in = td.nq;
-                        // a big level (one shard): the apply passes over every row instead of a touched list
-                        td.rowapply = !td_shard && tune().msbfs_td_rowapply > 0 &&
-                                      td.mf * tune().msbfs_td_rowapply >= sh.rows;
-                        if (td.mf > 0) {
-                            MsTd a{td.queue[qc].get(), td.qoff[qc].get(), td.nq, td.mf, c.push->row_ptr.get(),
-                                   c.push->col.get(), t.F[cur].get(), t.vis.get(), t.F[cur ^ 1].get(), td.touched.get(),
-                                   td.touched_off.get(), td.ctr.get() + 1, td_shard ? sh.halo_both.tbits : 31,
-                                   td_shard ? td.hs.get() : nullptr, td.hlist.get(), td.hlist_off.get(), td.ctr.get() + 2,
-                                   td_shard && td.pcnt.size() ? td.pcnt.get() : nullptr, sh.index, g.P,
-                                   // the first top-down levels skip the visited probe: next to nothing is visited
-                                   // yet, and it is a random 8-byte read per edge (RMAT-26 level 1: 33.6 M)
-                                   level >= tune().msbfs_td_noprobe ? 1 : 0, td.rowapply ? 1 : 0};
-                            msbfs_td_kernel<<<(unsigned)std::min<int64_t>(std::max<int64_t>(
-                                                  (td.mf / kTdEdgesPerThread + kBlock - 1) / kBlock, 1), tune().bfs_grid),
-                                              kBlock, 0, sh.stream>>>(a);
-                            JG_LAUNCH_CHECK();
-                            if (td_shard && td.pcnt.size()) {  // the set slots per peer (the sparse exchange's sizes)
-                                msbfs_slot_hist_kernel<<<(unsigned)kRedBlocks, kRedThreads, 0, sh.stream>>>(
-                                    td.hlist.get(), td.ctr.get() + 2, sh.halo_both.tbits, sh.index, g.P, td.bcount.get(),
-                                    td.pcnt.get());
-                                JG_LAUNCH_CHECK();
-                            }
-                        }
-                        fv.push_back(td.hs.peer());
-                        rv.push_back(td.rbuf.peer());
-                    }
-                    // sparse: only the set staging slots travel, as (offset, word) pairs, when they are fewer
-                    // than half the halo slots over all shards (the tail levels and the first levels from
-                    // the sources set a few thousand)
-                    bool sparse_done = false;
-                    if (td_shard && tune().msbfs_sparse) {
-                        const int P = g.P;
-                        std::vector<std::vector<int64_t>> cnt(g.shards.size(), std::vector<int64_t>((size_t)P, 0));
-                        std::vector<int64_t> mat((size_t)P * P + 1, 0);
-                        for (size_t i = 0; i < g.shards.size(); ++i) {
-                            Shard& sh = *g.shards[i];
-                            DeviceGuard dg(sh);
-                            // per-peer slot counts: the top-down kernel counted the slots it set first
-                            std::vector<unsigned long long> c((size_t)P);
-                            copy_d2h(c.data(), tds[i].pcnt.get(), (size_t)P * sizeof(unsigned long long), sh.stream);
-                            for (int q = 0; q < P; ++q) {
-                                cnt[i][(size_t)q] = (int64_t)c[(size_t)q];
-                                mat[(size_t)sh.index * P + q] = (int64_t)c[(size_t)q];
-                            }
-                            mat[(size_t)P * P] += sh.halo_both.recv_off[(size_t)P];  // the dense exchange's words
-                        }
-                        allreduce_sum_i64(g, mat.data(), P * P + 1);
-                        int64_t pairs_all = 0;
-                        for (int64_t k = 0; k < (int64_t)P * P; ++k) pairs_all += mat[(size_t)k];
-                        if (2 * pairs_all < mat[(size_t)P * P]) {
-                            const size_t ns_ = g.shards.size();
-                            std::vector<const char*> sp(ns_);
-                            std::vector<char*> rp(ns_);
-                            std::vector<std::vector<int64_t>> so(ns_), sc(ns_), ro(ns_), rc(ns_);
-                            for (size_t i = 0; i < ns_; ++i) {
-                                Shard& sh = *g.shards[i];
-                                DeviceGuard dg(sh);
-                                so[i].assign((size_t)P + 1, 0);
-                                ro[i].assign((size_t)P + 1, 0);
-                                sc[i].assign((size_t)P, 0);
-                                rc[i].assign((size_t)P, 0);
-                                PairRuns pk{}, pv{};
-                                pk.P = pv.P = P;
-                                for (int q = 0; q < P; ++q) {
-                                    so[i][(size_t)q + 1] = so[i][(size_t)q] + cnt[i][(size_t)q];
-                                    const int64_t from_q = mat[(size_t)q * P + sh.index];
-                                    ro[i][(size_t)q + 1] = ro[i][(size_t)q] + from_q;
-                                    sc[i][(size_t)q] = 2 * cnt[i][(size_t)q];  // uint64 elements: two per pair
-                                    rc[i][(size_t)q] = 2 * from_q;
-                                }
-                                for (int q = 0; q <= P; ++q) {
-                                    pk.off[q] = so[i][(size_t)q];
-                                    pv.off[q] = ro[i][(size_t)q];
-                                    pv.send_off[q] = sh.halo_both.send_off[(size_t)q];
-                                }
-                                const int64_t nh = so[i][(size_t)P];
-                                if (nh > 0) {
-                                    msbfs_pair_pack_kernel<<<(unsigned)kRedBlocks, kRedThreads, 0, sh.stream>>>(
-                                        tds[i].hlist.get(), nh, tds[i].hs.get(), sh.halo_both.tbits, sh.index, pk,
-                                        tds[i].bcount.get(), tds[i].pairs.get());
-                                    JG_LAUNCH_CHECK();
-                                }
-                                for (int q = 0; q <= P; ++q) {
-                                    so[i][(size_t)q] *= 2;
-                                    ro[i][(size_t)q] *= 2;
-                                }
-                                sp[i] = reinterpret_cast<const char*>(tds[i].pairs.get());
-                                rp[i] = reinterpret_cast<char*>(tds[i].rpairs.get());
-                                tds[i].nrp = ro[i][(size_t)P] / 2;
-                                tds[i].pv = pv;
-                            }
-                            exchange_runs(g, sp, so, sc, rp, ro, rc, sizeof(unsigned long long), ncclUint64);
-                            for (size_t i = 0; i < ns_; ++i) {
-                                Shard& sh = *g.shards[i];
-                                DeviceGuard dg(sh);
-                                if (tds[i].nrp > 0) {
-                                    msbfs_td_recv_pairs_kernel<<<grid_for(tds[i].nrp), kBlock, 0, sh.stream>>>(
-                                        tds[i].rpairs.get(), tds[i].nrp, tds[i].pv, sh.halo_both.send_src.get(),
-                                        st[i].vis.get(), st[i].F[cur ^ 1].get(), tds[i].touched.get(),
-                                        tds[i].touched_off.get(), tds[i].ctr.get() + 1);
-                                    JG_LAUNCH_CHECK();
-                                }
-                            }
-                            sparse_done = true;
-                            if (debug_bfs())
-                                std::fprintf(stderr, "[jg msbfs] level %d top-down, sparse reverse exchange: %lld pairs (dense: %lld words)\n",
-                                             level, (long long)pairs_all, (long long)mat[(size_t)P * P]);
-                        }
-                    }
-                    if (td_shard && !sparse_done) {
-                        exchange_halo_reverse(g, JG_ADJ_BOTH, fv, rv, sizeof(unsigned long long), ncclUint64);
-                        for (size_t i = 0; i < g.shards.size(); ++i) {
-                            Shard& sh = *g.shards[i];
-                            DeviceGuard dg(sh);
-                            const int64_t nrecv = sh.halo_both.send_off[g.P];
-                            if (nrecv > 0) {
-                                msbfs_td_recv_kernel<<<grid_for(nrecv, kBlock, 256 * 8), kBlock, 0, sh.stream>>>(
-                                    tds[i].rbuf.get(), sh.halo_both.send_src.get(), nrecv, st[i].vis.get(),
-                                    st[i].F[cur ^ 1].get(), tds[i].touched.get(), tds[i].touched_off.get(),
-                                    tds[i].ctr.get() + 1);
-                                JG_LAUNCH_CHECK();
-                            }
-                        }
-                    }
-                    for (size_t i = 0; i < g.shards.size(); ++i) {
-                        Shard& sh = *g.shards[i];
-                        DeviceGuard dg(sh);
-                        const BfsCsrs c = pick_csrs(sh, direction);
-                        St& t = st[i];
-                        Td& td = tds[i];
-                        // counts stay on the device (the apply and the clearing read them there): one host
-                        // read-back per level, read_frontier's
-                        if (td_shard) {  // the staging slots went out with the reverse exchange: back to zero
-                            msbfs_zero_list_packed_kernel<<<grid_for(sh.halo_both.recv_off[(size_t)g.P]), kBlock, 0, sh.stream>>>(
-                                td.hs.get(), td.hlist.get(), td.ctr.get() + 2);
-                            JG_LAUNCH_CHECK();
-                        }
-                        td_entries += (double)td.mf;
-                        if (debug_bfs())
-                            std::fprintf(stderr, "[jg msbfs] level %d top-down (shard %d): %lld frontier rows, %lld push entries\n",
-                                         level, sh.index, (long long)td.nq, (long long)td.mf);
-                        td_queued += (double)td.nq;
-                        if (td.rowapply) td_row_passes += (double)pull_live_rows(sh, c);
-                        {
-                            MsBfsOp op;
-                            op.F = t.F[cur].get();
-                            op.Fout = t.F[cur ^ 1].get();
-                            op.visited = t.vis.get();
-                            op.depth = t.depth.get();
-                            op.depth8 = t.depth8.get();
-                            op.nwl = nullptr;  // recorded from the next queue below (msbfs_td_record_kernel)
-                            op.changed = t.changed.get();
-                            op.rows = sh.rows;
-                            op.pos = g.vec_pos(sh, adj_of(sh, c));
-                            op.lvl = level + 1;
-                            op.live = t.live.get() + 1;
-                            // (the row-order apply stops at the pull adjacency's empty suffix: a push target has a
-                            // pull entry, so no row past it gains a bit after level 0; RMAT-26 BOTH: 34 of 67 M rows)
-                            if (td.rowapply)
-                                msbfs_td_apply_rows_kernel<<<grid_for(pull_live_rows(sh, c)), kBlock, 0, sh.stream>>>(
-                                    pull_live_rows(sh, c), op, c.push->row_ptr.get(), td.queue[qc ^ 1].get(),
-                                    td.qoff[qc ^ 1].get(), td.ctr.get(), t.live.get());
-                            else
-                                msbfs_td_apply_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(
-                                    td.touched.get(), td.ctr.get() + 1, op, c.push->row_ptr.get(), td.queue[qc ^ 1].get(),
-                                    td.qoff[qc ^ 1].get(), td.ctr.get(), t.live.get());
-                            JG_LAUNCH_CHECK();
-                        }
-                    }
-                    read_frontier(&td_touched);
-                    if (level + 1 < kMsLevelWords)
-                        for (size_t i = 0; i < g.shards.size(); ++i) {  // the level's depths: its new queue
-                            Shard& sh = *g.shards[i];
-                            DeviceGuard dg(sh);
-                            St& t = st[i];
-                            const int64_t nq = tds[i].nq;
-                            t.recs.emplace_back();
-                            St::Rec& r = t.recs.back();
-                            r.level = level + 1;
-                            r.n = nq;
-                            r.rows.alloc(std::max<int64_t>(nq, 1));
-                            r.words.alloc(std::max<int64_t>(nq, 1));
-                            if (nq > 0) {
-                                msbfs_td_record_kernel<<<grid_for(nq), kBlock, 0, sh.stream>>>(
-                                    tds[i].queue[qc ^ 1].get(), nq, t.F[cur ^ 1].get(),
-                                    g.vec_pos(sh, adj_of(sh, pick_csrs(sh, direction))), r.rows.get(), r.words.get());
-                                JG_LAUNCH_CHECK();
-                            }
-                        }
-                    combine_live();
-                    qc ^= 1;
-                    queued = live_ready = true;
-                    need_fwd = td_shard;
-                    prev_td = true;
-                } else {
-                    prev_td = false;
-                    if (need_fwd) {  // stale halo segments: the lazy forward exchange
-                        std::vector<void*> bufs;
-                        for (auto& t : st) bufs.push_back(t.F[cur].peer());
-                        exchange_vec(g, adj0, bufs, sizeof(unsigned long long), ncclUint64);
-                        need_fwd = false;
-                    }
-                    for (size_t i = 0; i < g.shards.size(); ++i) {
-                        Shard& sh = *g.shards[i];
-                        DeviceGuard dg(sh);
-                        const BfsCsrs c = pick_csrs(sh, direction);
-                        const PullPlan& plan = (c.pull == &sh.both) ? sh.plan_both : sh.plan_in;
-                        St& t = st[i];
-                        // (with the top-down path the frontier count ends the traversal: no changed flag, whose
-                        // one-word store every gaining row's wave would repeat)
-                        if (!td_ok) JG_HIP(hipMemsetAsync(t.changed.get(), 0, sizeof(int32_t), sh.stream));
-                        // rows without pull entries are not written by a pull level: a source among them keeps
-                        // its level-0 word in this output vector unless cleared here, and the frontier scan would
-                        // count it (one extra level)
-                        if (td_ok && c.pull->empty_from >= 0 &&
-                            c.pull->empty_from < sh.rows && !tds[i].src_rows.empty()) {
-                            msbfs_zero_tail_sources_kernel<<<1, kWave, 0, sh.stream>>>(
-                                t.F[cur ^ 1].get(), tds[i].srcs.get(), (int)tds[i].src_rows.size(), c.pull->empty_from);
-                            JG_LAUNCH_CHECK();
-                        }
-                        MsBfsOp op;
-                        op.F = t.F[cur].get();
-                        op.Fout = t.F[cur ^ 1].get();
-                        op.visited = t.vis.get();
-                        op.depth = t.depth.get();
-                        op.depth8 = t.depth8.get();
-                        op.nwl = level + 1 < kMsLevelWords ? t.nwl.get() + (int64_t)(level + 1) * sh.rows : nullptr;
-                        op.changed = td_ok ? nullptr : t.changed.get();
-                        op.rows = sh.rows;
-                        op.pos = g.vec_pos(sh, adj_of(sh, c));
-                        op.lvl = level + 1;
-                        // Live bits: the sources present in some word of this level's gathered vector.  A row
-                        // none of whose unvisited bits is live gains nothing, so the light rows skip it
-                        // (MsBfsOp::active) and the split skips every merge task whose rows are all such
-                        // (their partials are then stale, and finalize's live mask discards them).  At
-                        // RMAT-26 the last pull level has ~all rows done and the one before ~40% of band 0.
-                        unsigned long long* lw = t.live.get();
-                        if (!have_live) {
-                            const int64_t vlen = g.vec_len(sh, adj_of(sh, c));
-                            JG_HIP(hipMemsetAsync(lw, 0, sizeof(unsigned long long), sh.stream));
-                            msbfs_live_kernel<<<red_grid(vlen), kRedThreads, 0, sh.stream>>>(t.F[cur].get(), vlen, lw);
-                            JG_LAUNCH_CHECK();
-                        }
-                        op.live = lw;
-                        // msbfs_skip_first: no task bitmaps on the traversal's first pull level (few rows can be
-                        // done there; every task runs, the finalize's live mask keeps it exact)
-                        const bool no_bitmaps = pull_levels == 0;
-                        // msbfs_exit 1: every row with entries exits early on pull levels where fewer than
-                        // msbfs_exit_live permille of band 0's merge tasks hold a row that can still gain a bit
-                        // (their live count is read back once); 2: on every pull level
-                        const MsBu& bx = t.bx;
-                        int64_t exit_rows = bx.rows > 0 && tune().msbfs_exit == 2 ? bx.rows : 0;
-                        const bool exit_probe = bx.rows > 0 && tune().msbfs_exit == 1 && !no_bitmaps && !t.todo.empty();
-                        std::vector<const uint32_t*> tl;
-                        for (size_t b = 0; b < t.todo.size() && !no_bitmaps && !exit_rows; ++b) {
-                            const SliceBand& bd = *plan.bands[b];
-                            if (bd.tasks == 0 || bd.rows() == 0) {
-                                tl.push_back(nullptr);
-                                continue;
-                            }
-                            msbfs_todo_kernel<<<grid_for(bd.rows()), kBlock, 0, sh.stream>>>(
-                                t.vis.get(), bd.row_begin, bd.rows(), lw, t.todo[b].get());
-                            JG_LAUNCH_CHECK();
-                            // band 0 counts its live tasks apart (work[3]), and the count decides: an exit level
-                            // builds no bitmaps for the other bands
-                            const bool probe = exit_probe && b == 0;
-                            if (probe) JG_HIP(hipMemsetAsync(t.work.get() + 3, 0, sizeof(unsigned long long), sh.stream));
-                            msbfs_task_live_kernel<<<red_grid(bd.tasks), kRedThreads, 0, sh.stream>>>(
-                                bd.task_rows.get(), bd.tasks, t.todo[b].get(), t.tlive[b].get(),
-                                t.work.get() + (probe ? 3 : 0));
-                            JG_LAUNCH_CHECK();
-                            if (probe) {
-                                unsigned long long xlive = 0;
-                                copy_d2h(&xlive, t.work.get() + 3, sizeof xlive, sh.stream);
-                                const bool go = (double)xlive * 1000.0 < (double)t.exit_tasks * (double)tune().msbfs_exit_live;
-                                t.xlive_permille = t.exit_tasks ? (double)xlive * 1000.0 / (double)t.exit_tasks : 1000.0;
-                                if (debug_bfs())
-                                    std::fprintf(stderr, "[jg msbfs] level %d band 0: %llu of %lld merge tasks live -> %s\n",
-                                                 level, xlive, (long long)t.exit_tasks, go ? "early exit" : "merge");
-                                if (go) {
-                                    exit_rows = bx.rows;
-                                    break;
-                                }
-                                t.b0_live_merged += xlive;  // (work[0] holds the other bands' live tasks)
-                            }
-                            tl.push_back(reinterpret_cast<const uint32_t*>(t.tlive[b].get()));
-                        }
-                        if (no_bitmaps && i == 0) ++unskipped_levels;
-                        if (exit_rows) {  // every row with entries through the exit kernels, no merge launch
-                            t.exit_level_tasks += (double)t.all_tasks;
-                            if (no_bitmaps) t.exit_unskipped_tasks += (double)t.all_tasks;
-                            unsigned long long before = 0, after = 0;
-                            if (debug_bfs()) copy_d2h(&before, bx.examined, sizeof before, sh.stream);
-                            const unsigned xg = red_grid((bx.rows + 63) / 64 * kWave);
-                            msbfs_exit_first_kernel<<<xg, kRedThreads, 0, sh.stream>>>(bx, op, t.xrest.get());
-                            JG_LAUNCH_CHECK();
-                            msbfs_exit_rest_kernel<<<xg, kRedThreads, 0, sh.stream>>>(bx, op, t.xrest.get());
-                            JG_LAUNCH_CHECK();
-                            ++t.exit_all_levels;
-                            if (debug_bfs()) {
-                                copy_d2h(&after, bx.examined, sizeof after, sh.stream);
-                                std::fprintf(stderr, "[jg msbfs] level %d exit rows [0, %lld): %llu entries examined\n",
-                                             level, (long long)bx.rows, after - before);
-                            }
-                        } else {
-                            // rows without pull entries are not finalised: they gain nothing, their words are zero
-                            // on every output vector, and their new-bit words are masked at output
-                            // (msbfs_levels_to_planes_kernel)
-                            launch_pull(*c.pull, plan, op, t.hub.get(), sh.stream, ctx.profiling ? &ctx : nullptr, &sh,
-                                        t.split.size() ? t.split.get() : (unsigned long long*)nullptr, true,
-                                        tl.empty() ? nullptr : tl.data());
-                        }
-                        if (td_ok) {  // the next level's frontier counter (its direction) and, on one shard, live bits
-                            zero_words({{tds[i].ctr.get(), sizeof(unsigned long long)}, {lw, sizeof(unsigned long long)}},
-                                       sh.stream);
-                            // a level whose exit bands had (almost) no live task leaves a small frontier, which
-                            // the next level pushes top-down: its queue is built here, in the same pass
-                            const bool qnext = td_one && !t.todo.empty() && t.xlive_permille < (double)tune().msbfs_scan_queue;
-                            t.xlive_permille = 1000.0;
-                            // rows without pull entries gained nothing (a pull level does not finalise them):
-                            // the scans stop at the empty suffix (RMAT-26 BOTH: 34 M of 67 M rows)
-                            const int64_t ne = pull_live_rows(sh, c);
-                            if (qnext) {
-                                msbfs_frontier_live_kernel<<<grid_for((ne + 3) / 4), kBlock, 0, sh.stream>>>(
-                                    t.F[cur ^ 1].get(), ne, c.push->row_ptr.get(), tds[i].queue[qc ^ 1].get(),
-                                    tds[i].qoff[qc ^ 1].get(), tds[i].ctr.get(), lw);
-                                queued_next = true;
-                            } else {
-                                msbfs_scan_kernel<<<red_grid(ne), kRedThreads, 0, sh.stream>>>(
-                                    t.F[cur ^ 1].get(), ne, c.push->row_ptr.get(), lw, tds[i].ctr.get());
-                            }
-                            JG_LAUNCH_CHECK();
-                        }
-                    }
-                    if (td_ok) {
-                        read_frontier();
-                        combine_live();
-                        live_ready = true;
-                        if (queued_next) {  // the queue is in slot qc ^ 1 (one shard): the next top-down level's
-                            qc ^= 1;
-                            queued = true;
-                        }
-                    }
-                    ++pull_levels;
-                    need_fwd = g.P > 1;
-                }
-                int32_t any = 0;
-                if (td_ok) {
-                    // the level's new frontier (counted over all shards and ranks by read_frontier) is
-                    // exactly the rows that gained a bit: no read-back of the changed flags
-                    any = g_nq > 0;
-                } else {
-                    for (size_t i = 0; i < g.shards.size(); ++i) {
-                        Shard& sh = *g.shards[i];
-                        DeviceGuard dg(sh);
-                        int32_t ch = 0;
-                        JG_HIP(hipMemcpyAsync(&ch, st[i].changed.get(), sizeof ch, hipMemcpyDeviceToHost, sh.stream));
-                        JG_HIP(hipStreamSynchronize(sh.stream));
-                        any |= ch;
-                    }
-                    any = allreduce_or(g, any);
-                }
-                cur ^= 1;
-                ++level;
-                if (!any) break;
-            }
-            JG_HIP(hipEventRecord(t1, sh0.stream));
-            region_mark(sh0.stream, false);
-            JG_HIP(hipEventSynchronize(t1));
-            float ms = 0;
-            JG_HIP(hipEventElapsedTime(&ms, t0, t1));
-            total_ms += ms;
-            max_levels = std::max(max_levels, level);
-            // the work of this batch, counted after its timed region: per pull level 12 B per entry of a
-            // live merge task (col + gathered frontier word; a task streams its 512 slots) and of the light
-            // rows, 32 B per row (visited, the new frontier word, the level's new-bit word, the next
-            // level's live scan); per top-down level 12 B per frontier entry, 24 B per touched word and 8 B
-            // per queued vertex; past kMsLevelWords levels 4 B per reached (source, row) pair (a plane entry)
-            for (size_t i = 0; i < g.shards.size(); ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                St& t = st[i];
-                // one shard, BOTH: the visited words past the empty suffix were not cleared (the init); there only
-                // the source rows hold bits, one per source
-                const BfsCsrs cp = pick_csrs(sh, direction);
-                const int64_t prow = td_one && cp.pull == cp.push ? pull_live_rows(sh, cp) : sh.rows;
-                if (level >= kMsLevelWords) {  // the plane entries are counted only when planes were written
-                    msbfs_pairs_kernel<<<red_grid(prow), kRedThreads, 0, sh.stream>>>(t.vis.get(), prow,
-                                                                                       t.work.get() + 1);
-                    JG_LAUNCH_CHECK();
-                }
-                unsigned long long w[3] = {0, 0, 0};
-                copy_d2h(w, t.work.get(), sizeof w, sh.stream);
-                if (level >= kMsLevelWords && prow < sh.rows)
-                    for (int q = 0; q < ns; ++q)
-                        if (src_local[(size_t)q] >= prow && src_shard[(size_t)q] == sh.index) ++w[1];
-                const double live_tasks = t.todo.empty() ? (double)t.all_tasks * pull_levels - t.exit_level_tasks
-                                                          : (double)w[0] +
-                                                                (double)t.b0_live_merged +
-                                                                (double)t.all_tasks * unskipped_levels -
-                                                                t.exit_unskipped_tasks;
-                const double entries = live_tasks * kMergeTask + (double)t.light_nnz * (pull_levels - t.exit_all_levels) + (double)w[2];
-                work_entries += entries;
-                work_bytes += 12.0 * entries + 32.0 * (double)sh.rows * pull_levels +
-                              (level >= kMsLevelWords ? 4.0 * (double)w[1] : 0.0);
-            }
-            work_entries += td_entries;
-            work_bytes += 12.0 * td_entries + 24.0 * td_touched + 8.0 * td_queued + 8.0 * td_row_passes;
-            if (depth_rows || keep) {
-                materialize(level);  // the caller's int32 rows
-                if (depth_rows)
-                    for (size_t i = 0; i < g.shards.size(); ++i)
-                        for (int s = 0; s < ns; ++s)
-                            if (depth_rows[b0 + s])
-                                rows_to_dense(g, *g.shards[i], st[i].depth.peer() + (size_t)s * g.shards[i]->rows,
-                                              depth_rows[b0 + s]);
-                if (keep)  // the planes stay with their shards (jg_bfs_kept_row)
-                    for (size_t i = 0; i < g.shards.size(); ++i) g.shards[i]->kept_depth.swap(st[i].depth);
-            }
-        }
-        if (keep) g.kept_nsrc = nsrc;
-        ctx.last.compute_ms = total_ms;
-        ctx.last.levels = max_levels;
-        ctx.last.supersteps = max_levels;
-        ctx.last.algorithmic_bytes = work_bytes;
-        ctx.last.edges_traversed = work_entries;  // adjacency entries the levels examined
-        prof_collect(ctx, g);
-    }
+    Event t0, t1;  // the timed region of the single-shard and the batched engines (reused across batches)
+    if (sharded_do)
+        bfs_sharded_do(g, source_vids, max_depth, depth_rows, keep);
+    else if (single)
+        bfs_single(g, source_vids, direction, max_depth, depth_rows, keep, t0, t1);
+    else if (nsrc <= kNarrowMax && g.P == 1 && g.shards.size() == 1 && tune().bfs_narrow &&
+             pick_csrs(sh0, direction).push && pick_csrs(sh0, direction).pull)
+        bfs_narrow(g, source_vids, nsrc, direction, max_depth, depth_rows, keep);
+    else
+        bfs_batches(g, source_vids, nsrc, direction, max_depth, depth_rows, keep, t0, t1);
+    prof_collect(ctx, g);
 }
 
 // Sharded ShortestDistanceVertexProgram (weighted or unit): the same exact supersteps as the single

@@ -358,6 +358,45 @@ def test_msbfs_rows_past_the_suffix_are_never_read(ctx, oracle_lib, monkeypatch)
     g.close()
 
 
+@pytest.fixture(scope="module")
+def three_batches(oracle_lib):
+    """130 sources on RMAT-10 plus two isolated vertices: batches of 64, 64 and 2 of one call, with a source
+    twice in the first batch, a source in both the first and the second, an isolated source in the first
+    and in the last; the oracle's depth rows per direction."""
+    n0, vid0, src0, dst0, ds, dd = rmat_case(oracle_lib, 10)
+    n = n0 + 2
+    vid = np.concatenate([vid0, (np.arange(2, dtype=np.int64) + n0 + 1) << 8 | 7])
+    conn = np.random.default_rng(5).choice(np.unique(ds), 126, replace=False)
+    srcs = np.concatenate([conn[:62], [conn[5], n0], conn[62:125], [conn[0]], [conn[125], n0 + 1]])
+    assert len(srcs) == 130
+    want = {d: [oracle_lib.bfs(n, ds, dd, int(s), d) for s in srcs] for d in (1, 3)}
+    return n, vid, ds, dd, srcs, want
+
+
+@pytest.mark.parametrize("direction,shards", [(3, 1), (3, 3), (1, 1)])
+def test_msbfs_batches_share_no_state(oracle_lib, three_batches, direction, shards):
+    """Every batch of 64 sources starts from its own state: 130 sources in one call (64 + 64 + 2, the last
+    batch with a partial source mask) give the oracle's depth rows, again on a second call, and the rows
+    kept from the first 64 afterwards equal them too.  The level count is the deepest batch's (the level
+    that finds nothing new ends a batch)."""
+    import janusgraph_amd as jg
+    n, vid, ds, dd, srcs, want = three_batches
+    want = want[direction]
+    levels = max(max(int(w.max()) for w in want[b0:b0 + 64]) + 1 for b0 in range(0, len(srcs), 64))
+    c = jg.Context((0,) * shards)
+    g = c.build(vid, vid[ds], vid[dd], flags=ALL)
+    for call in range(2):
+        depth = g.bfs(vid[srcs], direction)
+        assert c.stats()["levels"] == levels, f"call {call}"
+        for k in range(len(srcs)):
+            np.testing.assert_array_equal(depth[k], want[k], err_msg=f"call {call}, source {k}")
+    g.bfs_keep(vid[srcs[:64]], direction)
+    for k in range(64):
+        np.testing.assert_array_equal(g.bfs_kept_row(k), want[k], err_msg=f"kept row {k}")
+    g.close()
+    c.close()
+
+
 @pytest.mark.parametrize("exit_mode", [0, 1, 2])
 def test_directed_multi_source_bfs(ctx, oracle_lib, exit_mode):
     """The 64-source BFS along OUT edges (pulling over the IN adjacency, pushing over OUT) with the early
