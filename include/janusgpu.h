@@ -66,7 +66,7 @@ extern "C" {
  * 3: jg_bfs_keep, jg_bfs_kept_row, jg_bfs_kept_release, jg_ctx_trim added.  Callers must check
  * jg_abi_version() == JG_ABI_VERSION before passing any struct across the ABI.
  * Still 3 (entry points only, no layout change): jg_builder_keep_labels, jg_builder_add_labeled_edges,
- * jg_builder_finish_labels added. */
+ * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -359,6 +359,36 @@ int jg_bfs_rows(jg_graph* g, const int64_t* source_vids, int32_t nsrc, int32_t d
 int jg_bfs_keep(jg_graph* g, const int64_t* source_vids, int32_t nsrc, int32_t direction, int32_t max_depth);
 int jg_bfs_kept_row(jg_graph* g, int32_t s, int32_t* depth_out);
 int jg_bfs_kept_release(jg_graph* g);
+
+/* The shortest-path predecessor DAG of kept row s (jg_bfs_keep), built on the device: what a path walk-back
+ * needs, without the adjacency rows crossing to the host.  target[n] (caller order, nullable = every
+ * reached vertex is a target).
+ *   Vertices: the reached targets (depth >= 0; the source too when it is a target) and every vertex on a
+ *     shortest path from the source to one of them.  If any target is reached the source is listed, with
+ *     an empty predecessor range.  No target reached: 0 vertices, 0 entries, deepest -1, JG_OK.
+ *   Order: non-increasing depth (the source last); inside one depth unspecified, but the same on every
+ *     call with the same arguments.
+ *   Predecessors of v at depth d: its distinct neighbours u with depth[u] == d - 1, each once, in the
+ *     order jg_graph_neighbors returns them, first occurrence kept (a multi-edge counts once, a self-loop
+ *     never).  The adjacency read is the reverse of the kept traversal's: JG_DIR_BOTH reads BOTH, a
+ *     JG_DIR_OUT traversal reads IN, a JG_DIR_IN traversal reads OUT; JG_ERR_UNSUPPORTED if it was not built.
+ *   deepest_out: the largest depth of a reached target.  All three outputs are nullable.
+ * The DAG stays with the graph until the next jg_bfs_kept_dag, jg_bfs_keep, jg_bfs_kept_release or
+ * jg_graph_destroy.  s outside [0, nsrc of the last jg_bfs_keep): JG_ERR_ARG.  One shard only: graphs of
+ * several shards (logical shards, rank mode) get JG_ERR_UNSUPPORTED and walk back on the host
+ * (jg_bfs_kept_row + jg_graph_neighbors).  Stats: compute_ms = the DAG build (HIP events; the target mask's
+ * copy in and the read-back are outside), levels = deepest, edges_traversed = the summed row lengths of the
+ * DAG vertices of depth >= 1, kernel_launches = launches of the walk kernels. */
+int jg_bfs_kept_dag(jg_graph* g, int32_t s, const uint8_t* target, int64_t* num_vertices_out,
+                    int64_t* num_entries_out, int32_t* deepest_out);
+/* DAG vertices [first, first + count): vertex_out[count] caller-order indices, depth_out[count],
+ * off_out[count + 1] ABSOLUTE offsets into the DAG's predecessor array, pred_out = its entries
+ * [off[first], off[first + count]) as caller-order indices.  Each pointer nullable (size first, then fill;
+ * a Java direct buffer holds 2 GiB, so a caller reads a large DAG in ranges).  No DAG held (never built, or
+ * dropped by a later jg_bfs_keep / jg_bfs_kept_release): JG_ERR_STATE; a range outside [0, num_vertices]:
+ * JG_ERR_ARG. */
+int jg_bfs_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
+                         int64_t* off_out, int32_t* pred_out);
 
 /* Adjacency of vertices rows[0, nrows) (output-order indices), in output-order indices: the host copy
  * of the snapshot a path walk-back reads where Fulgora re-reads each vertex's preloaded BOTH slice

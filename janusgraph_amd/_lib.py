@@ -44,6 +44,7 @@ EXPORTS = [
     "jg_builder_set_query_limit", "jg_bfs_rows", "jg_graph_neighbors", "jg_builder_set_weight_key",
     "jg_bfs_keep", "jg_bfs_kept_row", "jg_bfs_kept_release", "jg_ctx_trim",
     "jg_builder_keep_labels", "jg_builder_add_labeled_edges", "jg_builder_finish_labels",
+    "jg_bfs_kept_dag", "jg_bfs_kept_dag_read",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -196,6 +197,8 @@ def load():
         "jg_builder_keep_labels": ([_P], ctypes.c_int),
         "jg_builder_add_labeled_edges": ([_P, _P, _P, _P, _P, _i64], ctypes.c_int),
         "jg_builder_finish_labels": ([_P, _P, _i32, ctypes.c_uint32, _PP], ctypes.c_int),
+        "jg_bfs_kept_dag": ([_P, _i32, _P, _P, _P, _P], ctypes.c_int),
+        "jg_bfs_kept_dag_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -567,6 +570,55 @@ class Graph:
 
     def bfs_kept_release(self):
         check(load().jg_bfs_kept_release(self._h))
+
+    DAG_READ_ENTRIES = 1 << 28  # predecessors per jg_bfs_kept_dag_read call (1 GiB of int32)
+
+    def bfs_kept_dag_build(self, s, target=None):
+        """jg_bfs_kept_dag: builds the predecessor DAG of kept row s on the device (target: one flag per
+        vertex, None = every reached vertex).  Returns (num_vertices, num_entries, deepest)."""
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, np.uint8)
+            if t.ndim != 1 or len(t) != self.n:
+                raise ValueError("target needs one flag per vertex")
+        nv, ne, deepest = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        check(load().jg_bfs_kept_dag(self._h, int(s), _ptr(t), ctypes.byref(nv), ctypes.byref(ne),
+                                     ctypes.byref(deepest)))
+        return nv.value, ne.value, deepest.value
+
+    def bfs_kept_dag_read(self, first, count, want_pred=True):
+        """jg_bfs_kept_dag_read of the held DAG's vertices [first, first + count): (vertex, depth, off, pred)
+        with ABSOLUTE offsets; pred = entries [off[0], off[-1]) (None unless want_pred)."""
+        vertex = np.empty(max(count, 1), np.int32)
+        depth = np.empty(max(count, 1), np.int32)
+        off = np.empty(count + 1, np.int64)
+        check(load().jg_bfs_kept_dag_read(self._h, int(first), int(count), _ptr(vertex), _ptr(depth), _ptr(off), None))
+        pred = None
+        if want_pred:
+            k = int(off[-1] - off[0])
+            pred = np.empty(max(k, 1), np.int32)
+            check(load().jg_bfs_kept_dag_read(self._h, int(first), int(count), None, None, None, _ptr(pred)))
+            pred = pred[:k]
+        return vertex[:count], depth[:count], off, pred
+
+    def bfs_kept_dag(self, s, target=None):
+        """The predecessor DAG of kept row s (bfs_keep): (vertex, depth, off, pred).  vertex[j] (output-order
+        index, non-increasing depth[j], the source last) has the distinct predecessors
+        pred[off[j]:off[j + 1]] in jg_graph_neighbors order.  Built on the device (jg_bfs_kept_dag), read in
+        vertex ranges of at most DAG_READ_ENTRIES predecessors (a vertex with more is read alone)."""
+        nv, ne, _ = self.bfs_kept_dag_build(s, target)
+        if ne <= self.DAG_READ_ENTRIES:
+            return self.bfs_kept_dag_read(0, nv)
+        vertex, depth, off, _ = self.bfs_kept_dag_read(0, nv, want_pred=False)
+        pred = np.empty(ne, np.int32)
+        first = 0
+        while first < nv:
+            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
+            last = min(max(last, first + 1), nv)
+            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * int(off[first]))
+            check(load().jg_bfs_kept_dag_read(self._h, first, last - first, None, None, None, into))
+            first = last
+        return vertex, depth, off, pred
 
     def neighbors(self, rows, direction=DIR_BOTH):
         """jg_graph_neighbors: (off, nbr) CSR of the given output-order rows, in output-order indices."""

@@ -269,8 +269,11 @@ class GpuGraphComputer:
             b.close()
 
     def _shortest_paths(self, ctx, vp):
-        """ShortestPaths.execute of the Java drop-in: one depth row per source (jg_bfs_rows, 64 sources
-        per bit-parallel pass), paths rebuilt by PathDag over the snapshot's BOTH adjacency."""
+        """ShortestPaths.execute: 64 sources per bit-parallel pass.  On one shard the depth rows stay on the
+        device (jg_bfs_keep) and each source's predecessor DAG is built there (jg_bfs_kept_dag): only the DAG
+        comes back, and DevicePathDag enumerates it.  Sharded graphs take one depth row per source
+        (jg_bfs_rows) and PathDag walks back over the snapshot's BOTH adjacency on the host.  Both routes
+        give the same paths in the same order."""
         vid, src, dst, _ = self.graph.snapshot()
         index = {int(v): i for i, v in enumerate(vid.tolist())}
         sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
@@ -280,13 +283,19 @@ class GpuGraphComputer:
             target[[index[t] for t in vp.targets if t in index]] = True
         g = ctx.build(vid, src, dst, flags=_lib.ADJ_BOTH)
         paths, max_level = [], 0
+        max_depth = -1 if vp.max_distance is None else vp.max_distance
         try:
-            dag = PathDag(g.neighbors, len(vid))
+            on_device = g.info()["num_shards"] == 1
+            dag = DevicePathDag(len(vid)) if on_device else PathDag(g.neighbors, len(vid))
             for b0 in range(0, len(sources), SOURCES_PER_BFS):
                 batch = sources[b0:b0 + SOURCES_PER_BFS]
-                rows = g.bfs_rows(vid[batch], _lib.DIR_BOTH, -1 if vp.max_distance is None else vp.max_distance)
-                for s, depth in zip(batch, rows):
-                    got, deepest = dag.paths(depth, s, target)
+                if on_device:
+                    g.bfs_keep(vid[batch], _lib.DIR_BOTH, max_depth)
+                    results = (dag.paths(g.bfs_kept_dag(j, target), s, target) for j, s in enumerate(batch))
+                else:
+                    rows = g.bfs_rows(vid[batch], _lib.DIR_BOTH, max_depth)
+                    results = (dag.paths(depth, s, target) for s, depth in zip(batch, rows))
+                for got, deepest in results:
                     max_level = max(max_level, deepest)
                     paths.extend([int(vid[x]) for x in p] for p in got)
         finally:
@@ -367,3 +376,34 @@ class PathDag:
                 for u in reversed(pred[v].tolist()):  # first predecessor first, as the Java recursion
                     stack.append((u, suffix + [u]))
         return out, max(deepest, 0)
+
+
+class DevicePathDag:
+    """PathDag.paths' result from a predecessor DAG built on the device (Graph.bfs_kept_dag):
+    dag = (vertex, depth, off, pred), vertex[j] with the predecessors pred[off[j]:off[j + 1]], depth
+    non-increasing.  Paths are enumerated as PathDag does: targets ascending, first predecessor first."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def paths(self, dag, s, target=None):
+        """(paths as vertex-index lists, deepest target depth (0 if none))."""
+        vertex, depth, off, pred = dag
+        if len(vertex) == 0:
+            return [], 0
+        pos = np.full(self.n, -1, np.int64)
+        pos[vertex] = np.arange(len(vertex))
+        targets = np.sort(vertex if target is None else vertex[np.asarray(target, bool)[vertex]])
+        off = np.asarray(off).tolist()
+        out = []
+        for t in targets.tolist():
+            stack = [(t, [t])]
+            while stack:
+                v, suffix = stack.pop()
+                if v == s:
+                    out.append(list(reversed(suffix)))
+                    continue
+                j = pos[v]
+                for u in reversed(pred[off[j]:off[j + 1]].tolist()):
+                    stack.append((u, suffix + [u]))
+        return out, int(depth[0])

@@ -1483,6 +1483,22 @@ int jg_bfs_kept_release(jg_graph* g) {
     JG_GUARD_END
 }
 
+int jg_bfs_kept_dag(jg_graph* g, int32_t s, const uint8_t* target, int64_t* num_vertices_out,
+                    int64_t* num_entries_out, int32_t* deepest_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::bfs_kept_dag(g->impl, s, target, num_vertices_out, num_entries_out, deepest_out);
+    JG_GUARD_END
+}
+
+int jg_bfs_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
+                         int64_t* off_out, int32_t* pred_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::bfs_kept_dag_read(g->impl, first, count, vertex_out, depth_out, off_out, pred_out);
+    JG_GUARD_END
+}
+
 int jg_graph_neighbors(const jg_graph* g, int32_t direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                        int64_t* nbr_out) {
     JG_GUARD_BEGIN

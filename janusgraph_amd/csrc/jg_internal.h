@@ -263,6 +263,10 @@ struct Shard {
     int sd_hist[4] = {0, 0, 0, 0};  // delta-stepping: steps of the last calls (the first batch's size)
     int sd_hist_n = 0;
     DevBuf<int32_t> kept_depth;              // [kept_nsrc][rows] jg_bfs_keep's depth planes (jg_bfs_kept_row)
+    // the predecessor DAG of one kept row (jg_bfs_kept_dag, jg_pathdag.hip; Graph::dag_nv vertices, depth
+    // descending): caller-order vertex and depth, offsets into dag_pred, caller-order predecessors
+    DevBuf<int32_t> dag_vertex, dag_depth, dag_pred;
+    DevBuf<int64_t> dag_off;                 // [dag_nv + 1]
     // narrow bit-parallel BFS scratch (<= 8 sources, one shard; jg_narrow.hip), kept across calls
     std::vector<DevBuf<uint8_t>> nb_level;   // [levels][rows + pad] each level's frontier byte (= its new bits)
     DevBuf<uint8_t> nb_vis;                  // [rows] visited bits
@@ -306,6 +310,8 @@ struct Graph {
     // String-order ranks of the ids (graphs with BOTH; jg_cc.hip cc_prepare_ranks, at build): the id of
     // each rank on the first shard's device, its host copy made on first use (sharded CC output)
     int kept_nsrc = 0;  // depth rows kept by jg_bfs_keep
+    int kept_dir = 0;   // the direction of that traversal (jg_bfs_kept_dag reads the reverse adjacency)
+    int64_t dag_nv = -1, dag_ne = 0;  // the held predecessor DAG (Shard::dag_*); -1: none
     bool cc_ranks = false;
     DevBuf<int64_t> cc_vor;
     mutable std::vector<int64_t> cc_vor_host;
@@ -549,6 +555,11 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
              bool keep = false);
 void bfs_kept_row(Graph& g, int s, int32_t* depth_out);  // row s in caller order
 void bfs_kept_release(Graph& g);
+// jg_bfs_kept_dag / jg_bfs_kept_dag_read (jg_pathdag.hip): the predecessor DAG of kept row s, one shard
+void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out, int32_t* deepest_out);
+void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
+                       int64_t* off_out, int32_t* pred_out);
+void bfs_kept_dag_drop(Graph& g);
 // Zeroes the occupied positions of a shard's gathered vector of adjacency `adj` (own rows + peer runs).
 void zero_gathered(const Graph& g, const Shard& sh, uint32_t adj, void* v, size_t eb);
 // jg_graph_neighbors: the adjacency `direction` of caller vertices rows[0, nrows) in caller order

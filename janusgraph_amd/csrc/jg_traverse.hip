@@ -2994,6 +2994,7 @@ void zero_gathered(const Graph& g, const Shard& sh, uint32_t adj, void* v, size_
 }
 
 void bfs_kept_release(Graph& g) {
+    bfs_kept_dag_drop(g);
     for (auto& sp : g.shards) {
         DeviceGuard dg(*sp);
         sp->kept_depth.reset();
@@ -3996,6 +3997,7 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
     if (keep && nsrc > 64) fail(JG_ERR_ARG, "jg_bfs_keep takes at most 64 sources (one bit-parallel batch)");
     if (keep) bfs_kept_release(g);
     if (direction < JG_DIR_OUT || direction > JG_DIR_BOTH) fail(JG_ERR_ARG, "bad direction");
+    if (keep) g.kept_dir = direction;
     Ctx& ctx = *g.ctx;
     ctx.last = jg_stats{};
     prof_discard_exchanges(g);  // exchange pairs of this call only

@@ -231,6 +231,26 @@ JNIEXPORT jint JNICALL FN(bfsKeptRelease)(JNIEnv* env, jclass c, jlong g) {
     return jg_bfs_kept_release((jg_graph*)(intptr_t)g);
 }
 
+JNIEXPORT jint JNICALL FN(bfsKeptDag)(JNIEnv* env, jclass c, jlong g, jint s, jobject target, jlongArray out3) {
+    (void)c;
+    int64_t nv = 0, ne = 0;
+    int32_t deepest = -1;
+    int st = jg_bfs_kept_dag((jg_graph*)(intptr_t)g, s, (const uint8_t*)buf(env, target), &nv, &ne, &deepest);
+    if (st == JG_OK) {
+        jlong v[3] = {nv, ne, deepest};
+        (*env)->SetLongArrayRegion(env, out3, 0, 3, v);
+    }
+    return st;
+}
+
+JNIEXPORT jint JNICALL FN(bfsKeptDagRead)(JNIEnv* env, jclass c, jlong g, jlong first, jlong count, jobject vertex_out,
+                                          jobject depth_out, jobject off_out, jobject pred_out) {
+    (void)c;
+    return jg_bfs_kept_dag_read((jg_graph*)(intptr_t)g, first, count, (int32_t*)buf(env, vertex_out),
+                                (int32_t*)buf(env, depth_out), (int64_t*)buf(env, off_out),
+                                (int32_t*)buf(env, pred_out));
+}
+
 JNIEXPORT jint JNICALL FN(graphNeighbors)(JNIEnv* env, jclass c, jlong g, jint direction, jobject rows, jlong nrows,
                                           jobject off_out, jobject nbr_out) {
     (void)c;

@@ -96,6 +96,13 @@ final class JanusGpu {
     static native int bfsKeptRow(long graph, int s, ByteBuffer depthOut);
     /** jg_bfs_kept_release: frees the kept rows before the graph goes. */
     static native int bfsKeptRelease(long graph);
+    /** jg_bfs_kept_dag: builds the predecessor DAG of kept row s on the device (one shard; target: one byte
+     *  per vertex, null = every reached vertex); out3 = {vertices, predecessor entries, deepest}. */
+    static native int bfsKeptDag(long graph, int s, ByteBuffer target, long[] out3);
+    /** jg_bfs_kept_dag_read: DAG vertices [first, first + count) into direct buffers (each nullable): int32
+     *  vertices and depths, int64 absolute offsets (count + 1), int32 predecessors [off[first], off[first + count]). */
+    static native int bfsKeptDagRead(long graph, long first, long count, ByteBuffer vertexOut, ByteBuffer depthOut,
+                                     ByteBuffer offOut, ByteBuffer predOut);
     /** jg_graph_neighbors: rows (int64 output-order indices) -> offsets (int64, nrows + 1) and neighbours
      *  (int64 output-order indices; null: offsets only). */
     static native int graphNeighbors(long graph, int direction, ByteBuffer rows, long nrows, ByteBuffer offOut,
