@@ -66,7 +66,8 @@ extern "C" {
  * 3: jg_bfs_keep, jg_bfs_kept_row, jg_bfs_kept_release, jg_ctx_trim added.  Callers must check
  * jg_abi_version() == JG_ABI_VERSION before passing any struct across the ABI.
  * Still 3 (entry points only, no layout change): jg_builder_keep_labels, jg_builder_add_labeled_edges,
- * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added. */
+ * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added; jg_cc_census, jg_cc_census_read,
+ * jg_cc_census_release added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -404,6 +405,41 @@ int jg_graph_neighbors(const jg_graph* g, int32_t direction, const int64_t* rows
  * component label (the String-minimum id of v's weakly connected component).  iterations_out
  * (nullable) = supersteps of the synchronous program. */
 int jg_connected_components(jg_graph* g, int64_t* component_vid_out, int32_t* iterations_out);
+
+/* The component census of ConnectedComponentVertexProgram, made on the device: what TinkerPop's
+ * ClusterCountMapReduce / ClusterPopulationMapReduce (group().by(component).by(count())) compute from the
+ * program's result, without the n component ids crossing to the host.  jg_cc_census runs the program exactly
+ * as jg_connected_components(g, NULL, iterations_out) does (same path selection: union-find, propagation,
+ * the 99-superstep cap; same labels, same iterations_out) and then counts the vertices of each label there.
+ *   Component: a distinct label of the run, i.e. the vertex id whose decimal String is the minimum of the
+ *     component; its population = the vertices carrying that label.  A vertex without edges is its own
+ *     component of population 1.  When the 99-superstep cap binds, the census is of the labels the program
+ *     returns (what jg_connected_components would hand back), not of the true components.
+ *   num_components_out = all components; largest_out = the largest population (0 if the graph has no
+ *     vertex); num_listed_out = the components with population >= min_population: only these are held for
+ *     jg_cc_census_read.  min_population < 1: JG_ERR_ARG.  A min_population above the largest population
+ *     lists nothing and returns JG_OK.  Every output pointer is nullable.
+ *   Order of the listed components: population descending, ties by the label's decimal String ascending
+ *     (String.compareTo); the same on every call.
+ *   census_ms_out = HIP-event time of the census kernels alone.  Stats of the call: supersteps, levels and
+ *     edges_traversed as jg_connected_components reports them; compute_ms = the whole device span (the
+ *     program and the census); algorithmic_bytes = the program's model + the census's (jg_census.hip).
+ *   Errors as for jg_connected_components: JG_ERR_UNSUPPORTED for a graph built without JG_ADJ_BOTH or with
+ *     negative vertex ids.  One shard only: graphs of several shards (logical shards, rank mode) get
+ *     JG_ERR_UNSUPPORTED; callers fall back to jg_connected_components and group on the host.
+ * The census stays with the graph until the next jg_cc_census, jg_cc_census_release or jg_graph_destroy; a
+ * jg_connected_components, a traversal or any other program in between does not disturb it (it owns its
+ * buffers).  A failed jg_cc_census leaves no census held. */
+int jg_cc_census(jg_graph* g, int64_t min_population, int32_t* iterations_out, int64_t* num_components_out,
+                 int64_t* num_listed_out, int64_t* largest_out, double* census_ms_out);
+/* Listed components [first, first + count): component_vid_out[count] = their ids (vertex ids, as
+ * jg_connected_components returns them), population_out[count] = their populations.  Each pointer nullable
+ * (a Java direct buffer holds 2 GiB, so a caller reads a large census in ranges).  No census held:
+ * JG_ERR_STATE; a range outside [0, num_listed]: JG_ERR_ARG. */
+int jg_cc_census_read(jg_graph* g, int64_t first, int64_t count, int64_t* component_vid_out,
+                      int64_t* population_out);
+/* Drops the held census (JG_OK when none is held). */
+int jg_cc_census_release(jg_graph* g);
 
 /* Combiner vertex programs (the DegreeCounter family, janusgraph-test/.../olap/OLAPTest.java:424-503):
  * x_0 = init[v] (NULL: every vertex sends 1), then `steps` supersteps of

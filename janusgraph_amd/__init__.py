@@ -11,8 +11,8 @@ from .computer_types import (GraphComputerError, Persist, ProgramNotSupported, R
                              ResultMode)
 from .graph import InMemoryGraph, load_graph_of_the_gods  # noqa: F401
 from .idmanager import IDManager, VertexIDType  # noqa: F401
-from .programs import (CombinerVertexProgram, ConnectedComponentVertexProgram, DegreeCounter,  # noqa: F401
-                       DegreeMapper, PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
+from .programs import (ClusterCountMapReduce, ClusterPopulationMapReduce, CombinerVertexProgram,  # noqa: F401
+                       ConnectedComponentVertexProgram, DegreeCounter, DegreeMapper, PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
                        ShortestDistanceVertexProgram, ShortestPathVertexProgram)
 
 __all__ = [
@@ -21,5 +21,6 @@ __all__ = [
     "ProgramNotSupported", "Persist", "ResultGraph", "ResultMode", "InMemoryGraph", "load_graph_of_the_gods",
     "IDManager", "VertexIDType", "PageRankVertexProgram", "PageRankMapReduce", "ShortestDistanceVertexProgram",
     "ShortestDistanceMapReduce", "ConnectedComponentVertexProgram", "ShortestPathVertexProgram",
-    "CombinerVertexProgram", "DegreeCounter", "DegreeMapper", "COMBINE_SUM", "COMBINE_MIN", "COMBINE_MAX",
+    "CombinerVertexProgram", "DegreeCounter", "DegreeMapper", "ClusterCountMapReduce",
+    "ClusterPopulationMapReduce", "COMBINE_SUM", "COMBINE_MIN", "COMBINE_MAX",
 ]

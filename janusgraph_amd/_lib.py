@@ -45,6 +45,7 @@ EXPORTS = [
     "jg_bfs_keep", "jg_bfs_kept_row", "jg_bfs_kept_release", "jg_ctx_trim",
     "jg_builder_keep_labels", "jg_builder_add_labeled_edges", "jg_builder_finish_labels",
     "jg_bfs_kept_dag", "jg_bfs_kept_dag_read",
+    "jg_cc_census", "jg_cc_census_read", "jg_cc_census_release",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -199,6 +200,9 @@ def load():
         "jg_builder_finish_labels": ([_P, _P, _i32, ctypes.c_uint32, _PP], ctypes.c_int),
         "jg_bfs_kept_dag": ([_P, _i32, _P, _P, _P, _P], ctypes.c_int),
         "jg_bfs_kept_dag_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
+        "jg_cc_census": ([_P, _i64, _P, _P, _P, _P, _P], ctypes.c_int),
+        "jg_cc_census_read": ([_P, _i64, _i64, _P, _P], ctypes.c_int),
+        "jg_cc_census_release": ([_P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -653,3 +657,43 @@ class Graph:
         it = ctypes.c_int32(0)
         check(load().jg_connected_components(self._h, _ptr(comp), ctypes.byref(it)))
         return comp, int(it.value)
+
+    CENSUS_READ_COMPONENTS = 1 << 22  # components per jg_cc_census_read call (64 MiB of pairs)
+
+    def cc_census_build(self, min_population=1):
+        """jg_cc_census: runs ConnectedComponentVertexProgram and counts each component's vertices on the
+        device.  Returns (iterations, num_components, num_listed, largest, census_ms); the listed components
+        (population >= min_population) stay with the graph for cc_census_read."""
+        it = ctypes.c_int32(0)
+        nc, nl, largest = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        ms = ctypes.c_double(0)
+        check(load().jg_cc_census(self._h, int(min_population), ctypes.byref(it), ctypes.byref(nc), ctypes.byref(nl),
+                                  ctypes.byref(largest), ctypes.byref(ms)))
+        return int(it.value), nc.value, nl.value, largest.value, ms.value
+
+    def cc_census_read(self, first, count):
+        """jg_cc_census_read of the held census's listed components [first, first + count): (vids, populations)."""
+        vids = np.empty(max(count, 1), np.int64)
+        pops = np.empty(max(count, 1), np.int64)
+        check(load().jg_cc_census_read(self._h, int(first), int(count), _ptr(vids), _ptr(pops)))
+        return vids[:max(count, 0)], pops[:max(count, 0)]
+
+    def cc_census_release(self):
+        check(load().jg_cc_census_release(self._h))
+
+    def cc_census(self, min_population=1):
+        """The component census of ConnectedComponentVertexProgram: (iterations, num_components, largest, vids,
+        populations).  vids[j] is the id whose String labels the j-th listed component (population >=
+        min_population), populations[j] its vertex count; population descending, ties by the label's String.
+        Counted on the device (jg_cc_census): no per-vertex array is handed back; the pairs are read in ranges
+        of CENSUS_READ_COMPONENTS.  The census is released once read."""
+        it, nc, nl, largest, _ = self.cc_census_build(min_population)
+        vids = np.empty(nl, np.int64)
+        pops = np.empty(nl, np.int64)
+        for first in range(0, nl, self.CENSUS_READ_COMPONENTS):
+            k = min(self.CENSUS_READ_COMPONENTS, nl - first)
+            step = 8 * first
+            check(load().jg_cc_census_read(self._h, first, k, ctypes.c_void_p(vids.ctypes.data + step),
+                                           ctypes.c_void_p(pops.ctypes.data + step)))
+        self.cc_census_release()
+        return it, nc, largest, vids, pops

@@ -23,8 +23,9 @@ from . import _lib
 from .computer_types import (Persist, ProgramNotSupported, ResultGraph, ResultMode, computer_has_already_been_submitted,
                              computer_has_no_vertex_program_nor_map_reducers, graph_filter_not_supported)
 from .graph import InMemoryGraph
-from .programs import (CombinerVertexProgram, ConnectedComponentVertexProgram, PageRankVertexProgram,
-                       ShortestDistanceVertexProgram, ShortestPathVertexProgram)
+from .programs import (ClusterCountMapReduce, ClusterPopulationMapReduce, CombinerVertexProgram,
+                       ConnectedComponentVertexProgram, PageRankVertexProgram, ShortestDistanceVertexProgram,
+                       ShortestPathVertexProgram)
 
 
 class Memory:
@@ -98,6 +99,7 @@ class GpuGraphComputer:
         self.vertex_filter = None
         self.edge_filter = None
         self.executed = False
+        self._map_reduced = False  # the vertex program's route already filled the map-reduces' memory keys
 
     # ---- GraphComputer builder methods ----
     def vertices(self, vertex_filter):
@@ -188,7 +190,7 @@ class GpuGraphComputer:
             memory._iteration = iteration
             for k, v in extra.items():
                 memory.set(k, v)
-        for mr in self.map_reduces:
+        for mr in ([] if self._map_reduced else self.map_reduces):
             emitted = []
             for vid in (vids if vids is not None else []):
                 mr.map(int(vid), props.get(int(vid), {}), lambda k, v: emitted.append((k, v)))
@@ -226,6 +228,14 @@ class GpuGraphComputer:
             vid, src, dst, _ = g0.snapshot()
             g = ctx.build(vid, src, dst, flags=_lib.ADJ_BOTH)
             try:
+                if self._census_route(vp) and g.info()["num_shards"] == 1:
+                    # the map-reduces only group the labels: the census is made on the device
+                    # (jg_cc_census), no label is handed back and no per-vertex props are built
+                    it, count, _, cvid, cpop = g.cc_census(1)
+                    population = {str(int(c)): int(p) for c, p in zip(cvid, cpop)}
+                    self._map_reduced = True
+                    return vid, {}, it, {mr.memory_key: count if isinstance(mr, ClusterCountMapReduce)
+                                         else dict(population) for mr in self.map_reduces}
                 comp, it = g.connected_components()
             finally:
                 g.close()
@@ -251,6 +261,14 @@ class GpuGraphComputer:
             props = {int(v): {vp.property_key: int(d)} for v, d, k in zip(vid, x, keep) if k}
             return vid, props, vp.length, {}
         raise ProgramNotSupported(type(vp).__name__)
+
+    def _census_route(self, vp):
+        """Whether a ConnectedComponentVertexProgram submission needs the component census only: nothing is
+        persisted and every map-reduce is ClusterCountMapReduce / ClusterPopulationMapReduce over the
+        program's component property.  (The caller also needs a graph of one shard: jg_cc_census.)"""
+        return (self.persist_mode is Persist.NOTHING and bool(self.map_reduces)
+                and all(type(mr) in (ClusterCountMapReduce, ClusterPopulationMapReduce)
+                        and mr.cluster_property == vp.property for mr in self.map_reduces))
 
     def _label_scoped_graph(self, ctx, vid, src, dst, labels, flags):
         """The snapshot through a label-keeping builder, cut down to the typed scope's labels on the GPU

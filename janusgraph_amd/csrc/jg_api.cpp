@@ -1533,4 +1533,27 @@ int jg_connected_components(jg_graph* g, int64_t* component_vid_out, int32_t* it
     JG_GUARD_END
 }
 
+int jg_cc_census(jg_graph* g, int64_t min_population, int32_t* iterations_out, int64_t* num_components_out,
+                 int64_t* num_listed_out, int64_t* largest_out, double* census_ms_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::cc_census(g->impl, min_population, iterations_out, num_components_out, num_listed_out, largest_out,
+                  census_ms_out);
+    JG_GUARD_END
+}
+
+int jg_cc_census_read(jg_graph* g, int64_t first, int64_t count, int64_t* component_vid_out, int64_t* population_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::cc_census_read(g->impl, first, count, component_vid_out, population_out);
+    JG_GUARD_END
+}
+
+int jg_cc_census_release(jg_graph* g) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::cc_census_drop(g->impl);
+    JG_GUARD_END
+}
+
 }  // extern "C"

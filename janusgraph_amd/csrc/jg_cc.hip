@@ -1642,7 +1642,7 @@ void cc_propagation_init(Graph& g) {
 }
 }  // namespace
 
-void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out) {
+void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelHook* labels_hook) {
     if (!(g.flags & JG_ADJ_BOTH)) fail(JG_ERR_UNSUPPORTED, "connected components need a graph built with JG_ADJ_BOTH");
     Ctx& ctx = *g.ctx;
     ctx.last = jg_stats{};
@@ -1817,6 +1817,8 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out) {
     // the superstep cap, whose output is stale) make it here
     if (dev_out && !(solved && uf_one && out_done))
         emit_output(solved ? uf_labels : g.shards[0]->cc_label.get(), solved ? uf_label_rows : n);
+    // the census counts the same labels (jg_cc_census: one shard, no output array), inside the region
+    if (labels_hook) (*labels_hook)(solved ? uf_labels : sh0.cc_label.get(), solved ? uf_label_rows : sh0.rows);
     // with the output queued behind the BFS start, the BFS recorded t1 behind its last level batch (the
     // host's read of the final level state is control, as in the DO-BFS); otherwise it ends here
     if (!(dev_out && solved && uf_one && out_done)) {

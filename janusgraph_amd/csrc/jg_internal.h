@@ -267,6 +267,9 @@ struct Shard {
     // descending): caller-order vertex and depth, offsets into dag_pred, caller-order predecessors
     DevBuf<int32_t> dag_vertex, dag_depth, dag_pred;
     DevBuf<int64_t> dag_off;                 // [dag_nv + 1]
+    // the held component census (jg_cc_census, jg_census.hip; Graph::census_listed pairs, population
+    // descending): the component's vertex id and its population.  Its own buffers, not program scratch.
+    DevBuf<int64_t> census_vid, census_pop;
     // narrow bit-parallel BFS scratch (<= 8 sources, one shard; jg_narrow.hip), kept across calls
     std::vector<DevBuf<uint8_t>> nb_level;   // [levels][rows + pad] each level's frontier byte (= its new bits)
     DevBuf<uint8_t> nb_vis;                  // [rows] visited bits
@@ -312,6 +315,7 @@ struct Graph {
     int kept_nsrc = 0;  // depth rows kept by jg_bfs_keep
     int kept_dir = 0;   // the direction of that traversal (jg_bfs_kept_dag reads the reverse adjacency)
     int64_t dag_nv = -1, dag_ne = 0;  // the held predecessor DAG (Shard::dag_*); -1: none
+    int64_t census_listed = -1;       // the held component census (Shard::census_*); -1: none
     bool cc_ranks = false;
     DevBuf<int64_t> cc_vor;
     mutable std::vector<int64_t> cc_vor_host;
@@ -566,7 +570,16 @@ void zero_gathered(const Graph& g, const Shard& sh, uint32_t adj, void* v, size_
 void graph_neighbors(const Graph& g, int direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                      int64_t* nbr_out);
 void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* dist_out);
-void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out);
+// labels_hook (nullable): called inside the timed region once the run's labels are final on shard 0's stream,
+// with the labelled rows' String-order ranks label[0, lrows); rows [lrows, rows) are edgeless and carry
+// their own rank (Shard::cc_rank0).  jg_cc_census counts from there.
+using CcLabelHook = std::function<void(const int32_t* label, int64_t lrows)>;
+void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelHook* labels_hook = nullptr);
+// jg_cc_census / jg_cc_census_read / jg_cc_census_release (jg_census.hip): one shard
+void cc_census(Graph& g, int64_t min_population, int32_t* iterations_out, int64_t* components_out, int64_t* listed_out,
+               int64_t* largest_out, double* census_ms_out);
+void cc_census_read(Graph& g, int64_t first, int64_t count, int64_t* vid_out, int64_t* pop_out);
+void cc_census_drop(Graph& g);
 // Build time (graphs with BOTH): the String-order rank of every id (Graph::cc_vor, Shard::cc_rank0).
 void cc_prepare_ranks(Graph& g);
 // The union-find's result on one shard (jg_cc.hip): parent[v] is v's root for v < ne, minr[root] the

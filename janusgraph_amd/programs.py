@@ -290,5 +290,77 @@ class _MrBuilder:
         return self.cls(self.key)
 
 
+# TinkerPop's PeerPressureVertexProgram.CLUSTER, the property the cluster map-reduces read by default
+PEER_PRESSURE_CLUSTER = "gremlin.peerPressureVertexProgram.cluster"
+
+
+class _ClusterMrBuilder(_MrBuilder):
+    def __init__(self, cls):
+        super().__init__(cls)
+        self.cluster = PEER_PRESSURE_CLUSTER
+
+    def clusterProperty(self, key):  # noqa: N802
+        self.cluster = key
+        return self
+
+    def create(self):
+        return self.cls(self.key, self.cluster)
+
+
+class ClusterCountMapReduce(MapReduce):
+    """TinkerPop 3.4.6 ClusterCountMapReduce (third party, not in the container; [TP-recall]): every vertex
+    that has the cluster property emits it under one null key, the final result is the number of distinct
+    clusters (an int).  Default memory key "clusterCount"; the cluster property defaults to
+    PeerPressureVertexProgram.CLUSTER and is configurable (clusterProperty), e.g. to
+    ConnectedComponentVertexProgram's component key.  After that program, with Persist.NOTHING on one
+    shard, GpuGraphComputer takes the result from the device census (jg_cc_census) instead of this map."""
+
+    DEFAULT_MEMORY_KEY = "clusterCount"
+
+    def __init__(self, memory_key=DEFAULT_MEMORY_KEY, cluster_property=PEER_PRESSURE_CLUSTER):
+        self.memory_key = memory_key
+        self.cluster_property = cluster_property
+
+    @classmethod
+    def build(cls):
+        return _ClusterMrBuilder(cls)
+
+    def map(self, vid, props, emit):
+        c = props.get(self.cluster_property)
+        if c is not None:
+            emit(None, c)
+
+    def generate_final_result(self, key_values):
+        return len({v for _, v in key_values})
+
+
+class ClusterPopulationMapReduce(MapReduce):
+    """TinkerPop 3.4.6 ClusterPopulationMapReduce ([TP-recall], as above): every vertex that has the cluster
+    property emits (cluster, 1), the counts are summed per cluster, the final result is a dict cluster ->
+    population whose keys are the values the program stored (for ConnectedComponentVertexProgram: the label
+    Strings).  Default memory key "clusterPopulation"; cluster property as for ClusterCountMapReduce."""
+
+    DEFAULT_MEMORY_KEY = "clusterPopulation"
+
+    def __init__(self, memory_key=DEFAULT_MEMORY_KEY, cluster_property=PEER_PRESSURE_CLUSTER):
+        self.memory_key = memory_key
+        self.cluster_property = cluster_property
+
+    @classmethod
+    def build(cls):
+        return _ClusterMrBuilder(cls)
+
+    def map(self, vid, props, emit):
+        c = props.get(self.cluster_property)
+        if c is not None:
+            emit(c, 1)
+
+    def generate_final_result(self, key_values):
+        out = {}
+        for k, v in key_values:
+            out[k] = out.get(k, 0) + v
+        return out
+
+
 RECOGNISED = (PageRankVertexProgram, ShortestDistanceVertexProgram, ConnectedComponentVertexProgram,
               ShortestPathVertexProgram, CombinerVertexProgram)

@@ -268,6 +268,34 @@ JNIEXPORT jint JNICALL FN(connectedComponents)(JNIEnv* env, jclass c, jlong g, j
     return st;
 }
 
+JNIEXPORT jint JNICALL FN(ccCensus)(JNIEnv* env, jclass c, jlong g, jlong min_population, jlongArray out4,
+                                    jdoubleArray census_ms_out) {
+    (void)c;
+    int32_t it = 0;
+    int64_t nc = 0, nl = 0, largest = 0;
+    double ms = 0;
+    int st = jg_cc_census((jg_graph*)(intptr_t)g, min_population, &it, &nc, &nl, &largest, &ms);
+    if (st == JG_OK) {
+        jlong v[4] = {it, nc, nl, largest};
+        jdouble d = ms;
+        (*env)->SetLongArrayRegion(env, out4, 0, 4, v);
+        (*env)->SetDoubleArrayRegion(env, census_ms_out, 0, 1, &d);
+    }
+    return st;
+}
+
+JNIEXPORT jint JNICALL FN(ccCensusRead)(JNIEnv* env, jclass c, jlong g, jlong first, jlong count, jobject vid_out,
+                                        jobject population_out) {
+    (void)c;
+    return jg_cc_census_read((jg_graph*)(intptr_t)g, first, count, (int64_t*)buf(env, vid_out),
+                             (int64_t*)buf(env, population_out));
+}
+
+JNIEXPORT jint JNICALL FN(ccCensusRelease)(JNIEnv* env, jclass c, jlong g) {
+    (void)env; (void)c;
+    return jg_cc_census_release((jg_graph*)(intptr_t)g);
+}
+
 JNIEXPORT jint JNICALL FN(combineSteps)(JNIEnv* env, jclass c, jlong g, jint direction, jint combiner,
                                         jint int32_wrap, jobject init, jint steps, jobject out, jobject received_out) {
     (void)c;

@@ -108,6 +108,16 @@ final class JanusGpu {
     static native int graphNeighbors(long graph, int direction, ByteBuffer rows, long nrows, ByteBuffer offOut,
                                      ByteBuffer nbrOut);
     static native int connectedComponents(long graph, ByteBuffer componentVidOut, int[] iterationsOut);
+    /** jg_cc_census: runs the program and counts each component's vertices on the device (one shard);
+     *  out4 = {iterations, components, listed components (population >= minPopulation), largest population},
+     *  censusMsOut[0] = the census kernels' time. */
+    static native int ccCensus(long graph, long minPopulation, long[] out4, double[] censusMsOut);
+    /** jg_cc_census_read: listed components [first, first + count), population descending, into int64 direct
+     *  buffers (each nullable): the component's vertex id, its population. */
+    static native int ccCensusRead(long graph, long first, long count, ByteBuffer componentVidOut,
+                                   ByteBuffer populationOut);
+    /** jg_cc_census_release: drops the held census before the graph goes. */
+    static native int ccCensusRelease(long graph);
     /** jg_combine_steps: sum/min/max MessageCombiner programs (OLAPTest.DegreeCounter family). */
     static native int combineSteps(long graph, int direction, int combiner, int int32Wrap, ByteBuffer init, int steps,
                                    ByteBuffer out, ByteBuffer receivedOut);
