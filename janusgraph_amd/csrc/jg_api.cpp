@@ -234,10 +234,54 @@ void vdev_violation(int buffer_tag, int current_tag) {
 DirectFree::DirectFree() : prev(t_direct_free) { t_direct_free = true; }
 DirectFree::~DirectFree() { t_direct_free = prev; }
 
+namespace {
+std::atomic<int> g_dev_poison{-1};  // JG_DEV_POISON: the fill byte, or -1 (off); re-read at every context creation
+int dev_poison_env() {
+    const char* v = std::getenv("JG_DEV_POISON");
+    if (!v || !*v) return -1;
+    char* end = nullptr;
+    const unsigned long b = std::strtoul(v, &end, 16);
+    return end != v && *end == '\0' && b <= 0xff ? (int)b : -1;
+}
+}  // namespace
+
+void dev_poison_refresh() { g_dev_poison.store(dev_poison_env(), std::memory_order_relaxed); }
+
 void* dev_alloc(size_t bytes) {
     int dev = 0;
     (void)hipGetDevice(&dev);
-    return cache().alloc(dev, bytes);
+    void* p = cache().alloc(dev, bytes);
+    const int poison = g_dev_poison.load(std::memory_order_relaxed);
+    if (poison >= 0 && p) {
+        // the library's streams are non-blocking: the null stream is not ordered before them, so the fill
+        // is complete before the block is handed out (a ready block has nothing pending on it)
+        JG_HIP(hipMemsetAsync(p, poison, bytes, nullptr));
+        JG_HIP(hipStreamSynchronize(nullptr));
+    }
+    return p;
+}
+
+// tune key "dev_poison_probe" (tests): proves the switch is live.  A block of `bytes` is read back and must
+// hold the pattern in every byte; it is then overwritten with the complement, freed and synchronised, so the
+// second round draws the same block from the cache and must find the pattern again.
+void dev_poison_probe(int64_t bytes) {
+    const int poison = g_dev_poison.load(std::memory_order_relaxed);
+    if (poison < 0) fail(JG_ERR_STATE, "dev_poison_probe: JG_DEV_POISON is off");
+    if (bytes < 1 || bytes > (int64_t(1) << 26)) fail(JG_ERR_ARG, "dev_poison_probe: bytes must be in [1, 2^26]");
+    std::vector<uint8_t> host((size_t)bytes);
+    for (int round = 0; round < 2; ++round) {
+        DevBuf<uint8_t> d((size_t)bytes);
+        JG_HIP(hipMemcpy(host.data(), d.get(), (size_t)bytes, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < bytes; ++i)
+            if (host[(size_t)i] != (uint8_t)poison)
+                fail(JG_ERR_STATE, "dev_poison_probe: byte " + std::to_string(i) + " of a " +
+                                       (round ? "recycled" : "first") + " block is " + std::to_string(host[(size_t)i]) +
+                                       ", not the pattern " + std::to_string(poison));
+        JG_HIP(hipMemset(d.get(), ~poison & 0xff, (size_t)bytes));
+        JG_HIP(hipDeviceSynchronize());
+        d.reset();
+        dev_cache_sync();
+    }
 }
 
 void dev_free(void* p, size_t bytes, int dev) { cache().free(dev, p, bytes, t_direct_free); }
@@ -641,6 +685,10 @@ int jg_tune_set(const char* key, int64_t value) {
     JG_ARG(key, "null key");
     const std::string k(key);
     jg::Tune& t = jg::tune();
+    if (k == "dev_poison_probe") {  // not a knob: checks that JG_DEV_POISON fills blocks (jg_common.h)
+        jg::dev_poison_probe(value);
+        return JG_OK;
+    }
     // int knobs: name, field, allowed range
     struct Knob {
         const char* name;
@@ -753,6 +801,7 @@ int jg_ctx_create(const int* devices, int ndev, jg_ctx** out) {
     for (int i = 1; i < ndev; ++i) all_same &= devices[i] == devices[0];
     c.logical = ndev > 1 && all_same;
     jg::vdev_refresh();
+    jg::dev_poison_refresh();
     c.vdev = c.logical && jg::vdev_mode() != 0;
     if (ndev > 1 && !all_same) {
         std::vector<int> sorted(c.devices);
@@ -783,6 +832,7 @@ int jg_ctx_create_rank(int device, int nranks, int rank, const void* unique_id, 
     int count = 0;
     JG_HIP(hipGetDeviceCount(&count));
     JG_ARG(device >= 0 && device < count, "jg_ctx_create_rank: device ordinal out of range");
+    jg::dev_poison_refresh();
     auto ctx = std::make_unique<jg_ctx>();
     jg::Ctx& c = ctx->impl;
     c.devices = {device};
@@ -811,6 +861,7 @@ int jg_ctx_create_rank_transport(int device, int nranks, int rank, const jg_tran
     int count = 0;
     JG_HIP(hipGetDeviceCount(&count));
     JG_ARG(device >= 0 && device < count, "jg_ctx_create_rank_transport: device ordinal out of range");
+    jg::dev_poison_refresh();
     auto ctx = std::make_unique<jg_ctx>();
     jg::Ctx& c = ctx->impl;
     c.devices = {device};

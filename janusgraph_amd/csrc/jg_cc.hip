@@ -587,6 +587,16 @@ bool cc_union_find(Ctx& ctx, Shard& sh, int* iterations, const int32_t** labels,
     if (sh.cc_linked.size() != 1) sh.cc_linked.alloc(1);
     unsigned long long* linked = sh.cc_linked.get();  // read by the caller after its timed region
     JG_HIP(hipMemsetAsync(linked, 0, sizeof(unsigned long long), s));
+    if (ne == 0) {
+        // No row has an edge: every row is its own component, labelled by its own rank, in 0 supersteps.
+        // Nothing below would write parent[], and uf_giant_kernel's find from row 0 walked whatever the
+        // block held (a fresh block reads 0, its own root; a recycled one sent the walk anywhere).
+        *work_bytes = 0;
+        *iterations = 0;
+        *labels = parent;
+        *label_rows = 0;
+        return true;
+    }
     // rows of degree >= 64 (a property of the graph: found once, a binary search of the degree-sorted rows)
     if (sh.cc_heavy < 0) {
         heavy_rows_kernel<<<1, 1, 0, s>>>(c.row_ptr.get(), ne, sample.get());
@@ -1815,13 +1825,15 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelH
     }
     // the union-find queued the output behind its BFS start; the other paths (and a union-find that hit
     // the superstep cap, whose output is stale) make it here
-    if (dev_out && !(solved && uf_one && out_done))
+    // (an edgeless graph's union-find returns before its BFS and queues nothing: out_done is still false)
+    const bool out_queued = dev_out && solved && uf_one && out_done;
+    if (dev_out && !out_queued)
         emit_output(solved ? uf_labels : g.shards[0]->cc_label.get(), solved ? uf_label_rows : n);
     // the census counts the same labels (jg_cc_census: one shard, no output array), inside the region
     if (labels_hook) (*labels_hook)(solved ? uf_labels : sh0.cc_label.get(), solved ? uf_label_rows : sh0.rows);
     // with the output queued behind the BFS start, the BFS recorded t1 behind its last level batch (the
     // host's read of the final level state is control, as in the DO-BFS); otherwise it ends here
-    if (!(dev_out && solved && uf_one && out_done)) {
+    if (!out_queued) {
         JG_HIP(hipEventRecord(t1, sh0.stream));
         region_mark(sh0.stream, false);
     }

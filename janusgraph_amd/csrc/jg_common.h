@@ -36,7 +36,14 @@ void hip_check(hipError_t e, const char* what, const char* file, int line);
 // point that left blocks pending); only synchronised blocks are handed out again, so a block is never
 // reused while work queued before its free may still touch it (what hipFree guaranteed per call).
 // JG_NO_DEVCACHE=1 in the environment restores plain hipMalloc / hipFree.
+// JG_DEV_POISON=<hex byte> (test switch, e.g. ff or 2a; unset, empty or unparsable: off) fills the requested
+// bytes of every block dev_alloc hands out, fresh or recycled, with that byte before it returns: nothing
+// zeroes a block, so a kernel that reads what no one wrote then reads the pattern instead of whatever the
+// block held (tests/test_gpu_poison.py, DESIGN.md "Poisoned allocations").  Re-read at every context
+// creation; off, it costs one relaxed load per allocation.
 void* dev_alloc(size_t bytes);                 // current device; nullptr when the device is out of memory
+void dev_poison_refresh();                      // re-read JG_DEV_POISON (jg_ctx_create*)
+void dev_poison_probe(int64_t bytes);           // jg_tune_set("dev_poison_probe", bytes): fails unless blocks hold the pattern
 void dev_free(void* p, size_t bytes, int dev);
 void dev_cache_sync();                          // pending blocks of every device become reusable
 void dev_cache_release(int dev);                // synchronise and return every cached block of dev

@@ -3083,7 +3083,11 @@ void bfs_single(Graph& g, const int64_t* source_vids, int direction, int max_dep
         region_mark(sh.stream, true);
         JG_HIP(hipEventRecord(t0, sh.stream));
         levels = dobfs_single(ctx, sh, c, l, max_depth, depth.get(), &edges, nullptr, t1, full_init);
-        sh.bfs_depth_tail_clean = !full_init || live == sh.rows;
+        // A directed traversal inits every row (live == rows), but its source may be an isolated vertex
+        // inside BOTH's empty suffix: its 0 stays there too, and the next BOTH traversal must refill.
+        const Csr& b = sh.both;
+        const int64_t both_live = b.present() && b.empty_from >= 0 ? std::min(sh.rows, b.empty_from) : sh.rows;
+        sh.bfs_depth_tail_clean = l < both_live;
     }
     JG_HIP(hipEventSynchronize(t1));
     float ms = 0;

@@ -131,3 +131,54 @@ def test_bfs_64_sources(graphs, oracle_lib):
     depth = g.bfs(vid[srcs], jg.DIR_BOTH)
     for k in range(64):
         np.testing.assert_array_equal(depth[k], oracle_lib.bfs(n, s, t, int(srcs[k]), oracle_lib.DIR_BOTH), err_msg=f"source {k}")
+
+
+@pytest.mark.parametrize("shards", [1, 3])
+@pytest.mark.parametrize("bit", [5, 8])
+def test_temporal_schedule_at_a_small_shape(oracle_lib, bit, shards):
+    """The merge kernel's temporal schedule (merge_temporal = 2 forces it; by default only vectors past 64 MB
+    take it, RMAT-24 and larger): every block of an XCD sweeps the XCD's sub-slices in rounds and restages
+    its LDS image each round.  32 and 256 sub-slices give 4 and 32 rounds per XCD (at 8 sub-slices there is
+    one round, the static schedule); 3 logical shards take the multi-segment kernel.  The knob is read at
+    launch, so one graph runs both schedules: combiners and the 64-source BFS exactly, PageRank within
+    PR_RTOL of the oracle.  The ranks of the two schedules are equal bit for bit: a task belongs to a
+    sub-slice and writes its own partials, and the schedule only chooses which block (and round) takes it
+    (jg_pull.h pull_merge_kernel: h, g and G are all the schedule changes; task_of only permutes tasks)."""
+    import janusgraph_amd as jg
+    from janusgraph_amd import _lib
+    s, t = big_edges()
+    vid = (np.arange(N, dtype=np.int64) + 1) << 8
+    init = np.random.default_rng(bit).integers(-(1 << 39), 1 << 39, N)
+    deg = np.bincount(s, minlength=N) + np.bincount(t, minlength=N)
+    srcs = np.random.default_rng(5).choice(np.flatnonzero(deg > 0), 64, replace=False)
+    want_pr, _ = oracle_lib.pagerank(N, s, t, 0.85, N, 12)
+    ctx = None
+    try:
+        for k, v in (("band0_deg", 2), ("band0_bit", bit), ("band1_deg", 0)):
+            _lib.tune_set(k, v)
+        ctx = jg.Context((0,) * shards)
+        g = ctx.build(vid, vid[s], vid[t], flags=jg.ADJ_IN | jg.ADJ_OUT | jg.ADJ_BOTH)
+        assert g.info()["num_shards"] == shards
+        ranks = {}
+        for temporal in (0, 2):
+            _lib.tune_set("merge_temporal", temporal)
+            for combiner in (0, 1, 2):
+                for direction in (2, 1):
+                    want, wrec = oracle_lib.combine_steps(N, s, t, direction, combiner, 3, init, False)
+                    x, rec = g.combine_steps(direction, combiner, 3, init, False)
+                    np.testing.assert_array_equal(rec, wrec, err_msg=f"temporal {temporal} combiner {combiner} dir {direction}")
+                    np.testing.assert_array_equal(x, want, err_msg=f"temporal {temporal} combiner {combiner} dir {direction}")
+            depth = g.bfs(vid[srcs], jg.DIR_BOTH)
+            for k in range(64):
+                np.testing.assert_array_equal(depth[k], oracle_lib.bfs(N, s, t, int(srcs[k]), oracle_lib.DIR_BOTH),
+                                              err_msg=f"temporal {temporal} source {k}")
+            ranks[temporal], _ = g.pagerank(0.85, N, 12)
+            rel = np.abs(ranks[temporal] - want_pr) / np.maximum(np.abs(want_pr), 1e-300)
+            assert rel.max() <= PR_RTOL, f"temporal {temporal}: max rel err {rel.max()}"
+        np.testing.assert_array_equal(bits(ranks[2]), bits(ranks[0]), err_msg="temporal vs static schedule")
+    finally:
+        if ctx is not None:
+            ctx.close()
+        _lib.tune_set("merge_temporal", 1)
+        for k, v in DEFAULTS:
+            _lib.tune_set(k, v)
