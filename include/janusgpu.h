@@ -67,7 +67,7 @@ extern "C" {
  * jg_abi_version() == JG_ABI_VERSION before passing any struct across the ABI.
  * Still 3 (entry points only, no layout change): jg_builder_keep_labels, jg_builder_add_labeled_edges,
  * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added; jg_cc_census, jg_cc_census_read,
- * jg_cc_census_release added. */
+ * jg_cc_census_release added; jg_pagerank_top, jg_pagerank_top_read, jg_pagerank_top_release added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -326,6 +326,41 @@ int jg_pagerank(jg_graph* g, double damping, int64_t vertex_count, int32_t itera
 int jg_pagerank_begin(jg_graph* g, double damping, int64_t vertex_count);
 int jg_pagerank_step(jg_graph* g, int32_t nsteps);
 int jg_pagerank_end(jg_graph* g, double* rank_out, double* edge_count_out);
+
+/* The k highest-ranked vertices of the PageRank session the graph holds, selected on the device: what a
+ * PageRankMapReduce emission of n (vertex id, rank) pairs
+ * (janusgraph-backend-testutils/.../olap/PageRankMapReduce.java:62-67) followed by an ordering on the host
+ * computes, without the two n-element arrays of jg_pagerank_end crossing to the host.
+ *   Session: a jg_pagerank_begin plus any number of jg_pagerank_step calls, before or after jg_pagerank_end;
+ *     a jg_pagerank with iterations >= 1 also counts (begin, step, end).  A jg_pagerank with iterations == 0
+ *     runs nothing and leaves the held session, if any, as it was.  No session: JG_ERR_STATE.
+ *   Lists the first min(k, n) vertices of this total order: rank descending by numeric value, ties by the
+ *     caller-order index ascending (the order vid[] / the kept rows were given).  -0.0 orders as +0.0; a NaN
+ *     rank (a NaN damping) orders below every number and ties with other NaNs.  Ranks are only ordered, never
+ *     altered: the listed rank is the stored bit pattern.  k < 1: JG_ERR_ARG.
+ *   The call runs on the shards' streams behind the steps already enqueued and does not end or disturb the
+ *     session: steps may follow, and a later jg_pagerank_top sees the later ranks.  Straight after
+ *     jg_pagerank_begin every rank is 1/N, so it lists the indices 0 .. k-1.
+ *   num_listed_out = min(k, n); select_ms_out = HIP-event time of the select, order and emit kernels on the
+ *     first shard's stream.  Both nullable.  Stats of the call (a fresh jg_stats): compute_ms = the same
+ *     span, kernel_launches = the select's launches, algorithmic_bytes = its byte model (jg_top.hip).
+ *   Graphs of several in-process shards (jg_ctx_create with ndev > 1, a device listed more than once
+ *     included) are supported: each shard selects its own min(k, rows) and the records are merged on the
+ *     host.  Rank mode (jg_ctx_create_rank*): JG_ERR_UNSUPPORTED; callers fall back to jg_pagerank_end and
+ *     order on the host.
+ * The list stays with the graph until the next jg_pagerank_top, jg_pagerank_top_release or jg_graph_destroy;
+ * later steps, a new jg_pagerank_begin or any other program do not disturb it (it owns its storage).  A
+ * failed jg_pagerank_top leaves nothing held. */
+int jg_pagerank_top(jg_graph* g, int64_t k, int64_t* num_listed_out, double* select_ms_out);
+/* Listed records [first, first + count): vid_out[count] = the vertex ids, index_out[count] = their
+ * caller-order indices, rank_out[count] = janusgraph.pageRank.pageRank, edge_count_out[count] =
+ * janusgraph.pageRank.edgeCount (the out-degree as a double, as jg_pagerank_end returns it).  Each pointer
+ * nullable (a Java direct buffer holds 2 GiB, so a caller reads a large list in ranges).  Nothing held:
+ * JG_ERR_STATE; a range outside [0, num_listed]: JG_ERR_ARG. */
+int jg_pagerank_top_read(jg_graph* g, int64_t first, int64_t count, int64_t* vid_out, int64_t* index_out,
+                         double* rank_out, double* edge_count_out);
+/* Drops the held list (JG_OK when none is held). */
+int jg_pagerank_top_release(jg_graph* g);
 
 /* ShortestDistanceVertexProgram: dist_out[v] = min over paths v -> ... -> seed of <= max_depth hops
  * of the summed edge weights (int64; weights may be negative), or JG_DIST_ABSENT where Fulgora leaves

@@ -12,14 +12,14 @@ from .computer_types import (GraphComputerError, Persist, ProgramNotSupported, R
 from .graph import InMemoryGraph, load_graph_of_the_gods  # noqa: F401
 from .idmanager import IDManager, VertexIDType  # noqa: F401
 from .programs import (ClusterCountMapReduce, ClusterPopulationMapReduce, CombinerVertexProgram,  # noqa: F401
-                       ConnectedComponentVertexProgram, DegreeCounter, DegreeMapper, PageRankMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
+                       ConnectedComponentVertexProgram, DegreeCounter, DegreeMapper, PageRankMapReduce, PageRankTopMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
                        ShortestDistanceVertexProgram, ShortestPathVertexProgram)
 
 __all__ = [
     "Context", "Graph", "JanusGpuError", "load", "ADJ_IN", "ADJ_OUT", "ADJ_BOTH", "DIR_IN", "DIR_OUT", "DIR_BOTH",
     "LIB_PATH", "GpuGraphComputer", "ComputerResult", "ComputedGraph", "Memory", "GraphComputerError",
     "ProgramNotSupported", "Persist", "ResultGraph", "ResultMode", "InMemoryGraph", "load_graph_of_the_gods",
-    "IDManager", "VertexIDType", "PageRankVertexProgram", "PageRankMapReduce", "ShortestDistanceVertexProgram",
+    "IDManager", "VertexIDType", "PageRankVertexProgram", "PageRankMapReduce", "PageRankTopMapReduce", "ShortestDistanceVertexProgram",
     "ShortestDistanceMapReduce", "ConnectedComponentVertexProgram", "ShortestPathVertexProgram",
     "CombinerVertexProgram", "DegreeCounter", "DegreeMapper", "ClusterCountMapReduce",
     "ClusterPopulationMapReduce", "COMBINE_SUM", "COMBINE_MIN", "COMBINE_MAX",

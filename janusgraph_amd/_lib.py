@@ -46,6 +46,7 @@ EXPORTS = [
     "jg_builder_keep_labels", "jg_builder_add_labeled_edges", "jg_builder_finish_labels",
     "jg_bfs_kept_dag", "jg_bfs_kept_dag_read",
     "jg_cc_census", "jg_cc_census_read", "jg_cc_census_release",
+    "jg_pagerank_top", "jg_pagerank_top_read", "jg_pagerank_top_release",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -203,6 +204,9 @@ def load():
         "jg_cc_census": ([_P, _i64, _P, _P, _P, _P, _P], ctypes.c_int),
         "jg_cc_census_read": ([_P, _i64, _i64, _P, _P], ctypes.c_int),
         "jg_cc_census_release": ([_P], ctypes.c_int),
+        "jg_pagerank_top": ([_P, _i64, _P, _P], ctypes.c_int),
+        "jg_pagerank_top_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
+        "jg_pagerank_top_release": ([_P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -537,6 +541,36 @@ class Graph:
         ec = self._out(self.n, np.float64) if want else None
         check(load().jg_pagerank_end(self._h, _ptr(rank), _ptr(ec)))
         return rank, ec
+
+    def pagerank_top_build(self, k):
+        """jg_pagerank_top: selects the min(k, n) highest-ranked vertices of the held PageRank session on the
+        device (rank descending, ties by caller-order index ascending).  Returns (listed, select_ms); the list
+        stays with the graph for pagerank_top_read."""
+        listed = ctypes.c_int64(0)
+        ms = ctypes.c_double(0)
+        check(load().jg_pagerank_top(self._h, int(k), ctypes.byref(listed), ctypes.byref(ms)))
+        return listed.value, ms.value
+
+    def pagerank_top_read(self, first, count):
+        """jg_pagerank_top_read of the held list's records [first, first + count): (vid, index, rank,
+        edge_count)."""
+        m = max(count, 1)
+        vid, index = np.empty(m, np.int64), np.empty(m, np.int64)
+        rank, ec = np.empty(m, np.float64), np.empty(m, np.float64)
+        check(load().jg_pagerank_top_read(self._h, int(first), int(count), _ptr(vid), _ptr(index), _ptr(rank),
+                                          _ptr(ec)))
+        c = max(count, 0)
+        return vid[:c], index[:c], rank[:c], ec[:c]
+
+    def pagerank_top_release(self):
+        check(load().jg_pagerank_top_release(self._h))
+
+    def pagerank_top(self, k):
+        """The min(k, n) highest-ranked vertices of the held PageRank session, in order: (vid, index, rank,
+        edge_count).  Selected on the device (jg_pagerank_top): only the listed records are handed back.  The
+        list stays with the graph (pagerank_top_read, pagerank_top_release)."""
+        listed, _ = self.pagerank_top_build(k)
+        return self.pagerank_top_read(0, listed)
 
     def shortest_distance(self, seed_vid, max_depth):
         dist = self._out(self.n, np.int64)

@@ -24,8 +24,8 @@ from .computer_types import (Persist, ProgramNotSupported, ResultGraph, ResultMo
                              computer_has_no_vertex_program_nor_map_reducers, graph_filter_not_supported)
 from .graph import InMemoryGraph
 from .programs import (ClusterCountMapReduce, ClusterPopulationMapReduce, CombinerVertexProgram,
-                       ConnectedComponentVertexProgram, PageRankVertexProgram, ShortestDistanceVertexProgram,
-                       ShortestPathVertexProgram)
+                       ConnectedComponentVertexProgram, PageRankTopMapReduce, PageRankVertexProgram,
+                       ShortestDistanceVertexProgram, ShortestPathVertexProgram)
 
 
 class Memory:
@@ -209,6 +209,15 @@ class GpuGraphComputer:
                 return vid, {}, 0, {}
             g = ctx.build(vid, src, dst, flags=_lib.ADJ_IN)
             try:
+                if self._top_route(vp):
+                    # the map-reduces only want the highest ranks: the ranks stay on the device, the longest
+                    # list is selected there (jg_pagerank_top) and no per-vertex props are built
+                    g.pagerank_begin(vp.damping_factor, vp.vertex_count)
+                    g.pagerank_step(vp.max_iterations - 1)
+                    tvid, _, trank, _ = g.pagerank_top(max(mr.k for mr in self.map_reduces))
+                    top = [(int(v), float(r)) for v, r in zip(tvid, trank)]
+                    self._map_reduced = True
+                    return vid, {}, vp.max_iterations, {mr.memory_key: top[:mr.k] for mr in self.map_reduces}
                 rank, ec = g.pagerank(vp.damping_factor, vp.vertex_count, vp.max_iterations)
             finally:
                 g.close()
@@ -269,6 +278,13 @@ class GpuGraphComputer:
         return (self.persist_mode is Persist.NOTHING and bool(self.map_reduces)
                 and all(type(mr) in (ClusterCountMapReduce, ClusterPopulationMapReduce)
                         and mr.cluster_property == vp.property for mr in self.map_reduces))
+
+    def _top_route(self, vp):
+        """Whether a PageRankVertexProgram submission needs the highest-ranked vertices only: nothing is
+        persisted and every map-reduce is a PageRankTopMapReduce (each gets its own prefix of one device
+        list, jg_pagerank_top)."""
+        return (self.persist_mode is Persist.NOTHING and bool(self.map_reduces)
+                and all(type(mr) is PageRankTopMapReduce for mr in self.map_reduces))
 
     def _label_scoped_graph(self, ctx, vid, src, dst, labels, flags):
         """The snapshot through a label-keeping builder, cut down to the typed scope's labels on the GPU

@@ -1485,6 +1485,28 @@ int jg_pagerank(jg_graph* g, double damping, int64_t vertex_count, int32_t itera
     JG_GUARD_END
 }
 
+int jg_pagerank_top(jg_graph* g, int64_t k, int64_t* num_listed_out, double* select_ms_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::pagerank_top(g->impl, k, num_listed_out, select_ms_out);
+    JG_GUARD_END
+}
+
+int jg_pagerank_top_read(jg_graph* g, int64_t first, int64_t count, int64_t* vid_out, int64_t* index_out,
+                         double* rank_out, double* edge_count_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::pagerank_top_read(g->impl, first, count, vid_out, index_out, rank_out, edge_count_out);
+    JG_GUARD_END
+}
+
+int jg_pagerank_top_release(jg_graph* g) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::pagerank_top_drop(g->impl);
+    JG_GUARD_END
+}
+
 int jg_shortest_distance(jg_graph* g, int64_t seed_vid, int32_t max_depth, int64_t* dist_out) {
     JG_GUARD_BEGIN
     JG_ARG(g && dist_out, "null argument");

@@ -316,6 +316,11 @@ struct Graph {
     int kept_dir = 0;   // the direction of that traversal (jg_bfs_kept_dag reads the reverse adjacency)
     int64_t dag_nv = -1, dag_ne = 0;  // the held predecessor DAG (Shard::dag_*); -1: none
     int64_t census_listed = -1;       // the held component census (Shard::census_*); -1: none
+    // the held PageRank top list (jg_pagerank_top, jg_top.hip; top_listed records in the list's order): the
+    // caller-order index, rank and edgeCount of each, merged from the shards' selects and held on the host
+    int64_t top_listed = -1;          // -1: none
+    std::vector<int64_t> top_index;
+    std::vector<double> top_rank, top_edges;
     bool cc_ranks = false;
     DevBuf<int64_t> cc_vor;
     mutable std::vector<int64_t> cc_vor_host;
@@ -553,6 +558,11 @@ ScopeSelect scope_select(const int64_t* lab, const int64_t* src, const int64_t* 
 void pagerank_begin(Graph& g, double damping, int64_t vertex_count);
 void pagerank_steps(Graph& g, int nsteps);
 void pagerank_end(Graph& g, double* rank_out, double* edge_count_out);
+// jg_pagerank_top / jg_pagerank_top_read / jg_pagerank_top_release (jg_top.hip): the shards of one process
+void pagerank_top(Graph& g, int64_t k, int64_t* listed_out, double* select_ms_out);
+void pagerank_top_read(const Graph& g, int64_t first, int64_t count, int64_t* vid_out, int64_t* index_out,
+                       double* rank_out, double* edge_count_out);
+void pagerank_top_drop(Graph& g);
 // depth_rows[s] (each nullable, the array too): source s's depths in caller order (n int32)
 // keep: the depth rows stay on the device (Shard::kept_depth, Graph::kept_nsrc) for bfs_kept_row
 void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int max_depth, int32_t* const* depth_rows,

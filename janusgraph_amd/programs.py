@@ -290,6 +290,51 @@ class _MrBuilder:
         return self.cls(self.key)
 
 
+class _TopMrBuilder(_MrBuilder):
+    def __init__(self, cls):
+        super().__init__(cls)
+        self.k = 10
+
+    def limit(self, k):
+        self.k = int(k)
+        return self
+
+    def create(self):
+        return self.cls(self.k, self.key)
+
+
+class PageRankTopMapReduce(MapReduce):
+    """The k highest-ranked vertices of a PageRankVertexProgram run: memory[memory_key] = a list of (vertex id,
+    rank), rank descending by numeric value (-0.0 as +0.0, NaN last), ties in emission order, which is the
+    snapshot's vertex order.  This project's own class, not one of the reference's: it is what a
+    PageRankMapReduce emission followed by an ordering on the caller's side boils down to.  After
+    PageRankVertexProgram, with Persist.NOTHING and no other kind of map-reduce, GpuGraphComputer takes the
+    list from the device select (jg_pagerank_top) instead of this map."""
+
+    DEFAULT_MEMORY_KEY = "pageRankTop"
+
+    def __init__(self, k, memory_key=DEFAULT_MEMORY_KEY):
+        if int(k) < 1:
+            raise ValueError(f"k must be at least 1: {k}")
+        self.k = int(k)
+        self.memory_key = memory_key
+
+    @classmethod
+    def build(cls):
+        return _TopMrBuilder(cls)
+
+    def map(self, vid, props, emit):  # as PageRankMapReduce.map
+        v = props.get(PageRankVertexProgram.PAGE_RANK)
+        if v is not None:
+            emit(vid, v)
+
+    def generate_final_result(self, key_values):
+        def order(kv):
+            r = kv[1]
+            return (1, 0.0) if r != r else (0, -(r + 0.0))
+        return sorted(key_values, key=order)[:self.k]  # stable: ties keep emission order
+
+
 # TinkerPop's PeerPressureVertexProgram.CLUSTER, the property the cluster map-reduces read by default
 PEER_PRESSURE_CLUSTER = "gremlin.peerPressureVertexProgram.cluster"
 

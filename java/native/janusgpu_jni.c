@@ -296,6 +296,34 @@ JNIEXPORT jint JNICALL FN(ccCensusRelease)(JNIEnv* env, jclass c, jlong g) {
     return jg_cc_census_release((jg_graph*)(intptr_t)g);
 }
 
+JNIEXPORT jint JNICALL FN(pagerankTop)(JNIEnv* env, jclass c, jlong g, jlong k, jlongArray listed_out,
+                                       jdoubleArray select_ms_out) {
+    (void)c;
+    int64_t nl = 0;
+    double ms = 0;
+    int st = jg_pagerank_top((jg_graph*)(intptr_t)g, k, &nl, &ms);
+    if (st == JG_OK) {
+        jlong v = nl;
+        jdouble d = ms;
+        (*env)->SetLongArrayRegion(env, listed_out, 0, 1, &v);
+        (*env)->SetDoubleArrayRegion(env, select_ms_out, 0, 1, &d);
+    }
+    return st;
+}
+
+JNIEXPORT jint JNICALL FN(pagerankTopRead)(JNIEnv* env, jclass c, jlong g, jlong first, jlong count, jobject vid_out,
+                                           jobject index_out, jobject rank_out, jobject edge_count_out) {
+    (void)c;
+    return jg_pagerank_top_read((jg_graph*)(intptr_t)g, first, count, (int64_t*)buf(env, vid_out),
+                                (int64_t*)buf(env, index_out), (double*)buf(env, rank_out),
+                                (double*)buf(env, edge_count_out));
+}
+
+JNIEXPORT jint JNICALL FN(pagerankTopRelease)(JNIEnv* env, jclass c, jlong g) {
+    (void)env; (void)c;
+    return jg_pagerank_top_release((jg_graph*)(intptr_t)g);
+}
+
 JNIEXPORT jint JNICALL FN(combineSteps)(JNIEnv* env, jclass c, jlong g, jint direction, jint combiner,
                                         jint int32_wrap, jobject init, jint steps, jobject out, jobject received_out) {
     (void)c;

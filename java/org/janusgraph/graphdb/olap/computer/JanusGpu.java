@@ -118,6 +118,16 @@ final class JanusGpu {
                                    ByteBuffer populationOut);
     /** jg_cc_census_release: drops the held census before the graph goes. */
     static native int ccCensusRelease(long graph);
+    /** jg_pagerank_top: the min(k, n) highest-ranked vertices of the held PageRank session, selected on the
+     *  device (rank descending, ties by snapshot order); listedOut[0] = the records listed, selectMsOut[0] =
+     *  the select's device time.  The list stays with the graph for pagerankTopRead. */
+    static native int pagerankTop(long graph, long k, long[] listedOut, double[] selectMsOut);
+    /** jg_pagerank_top_read: listed records [first, first + count) into direct buffers (each nullable): int64
+     *  vertex ids and snapshot indices, double pageRank and edgeCount. */
+    static native int pagerankTopRead(long graph, long first, long count, ByteBuffer vidOut, ByteBuffer indexOut,
+                                      ByteBuffer rankOut, ByteBuffer edgeCountOut);
+    /** jg_pagerank_top_release: drops the held list before the graph goes. */
+    static native int pagerankTopRelease(long graph);
     /** jg_combine_steps: sum/min/max MessageCombiner programs (OLAPTest.DegreeCounter family). */
     static native int combineSteps(long graph, int direction, int combiner, int int32Wrap, ByteBuffer init, int steps,
                                    ByteBuffer out, ByteBuffer receivedOut);
