@@ -728,6 +728,8 @@ int jg_tune_set(const char* key, int64_t value) {
         {"bfs_grid", &t.bfs_grid, 64, 65536},
         {"bfs_tail_grid", &t.bfs_tail_grid, 0, 65536},
         {"merge_temporal", &t.merge_temporal, 0, 2},
+        {"merge_hot", &t.merge_hot, -1, 1 << 30},
+        {"merge_off32", &t.merge_off32, 0, 1},
         {"sd_delta", &t.sd_delta, -1, 1 << 30},
         {"sd_dist32", &t.sd_dist32, 0, 2},
     };

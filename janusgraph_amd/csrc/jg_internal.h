@@ -726,6 +726,11 @@ struct Tune {
                                       // 0 off, 1 when an XCD's eighth of the vector exceeds 8 MB, 2 always
     int merge_stage[4] = {-1, -1, -1, -1};  // per band: LDS window of a wave's task partials (slots; 0 = direct
                                           // stores, -1 = automatic from the band's heads per task)
+    int merge_hot = -1;               // read at launch: most hot entries of a vector segment that a band stages in LDS,
+                                      // 2^-bits of them per sub-slice image (-1: all that fit; rounded down to whole
+                                      // line groups, 16 << bits; 0: no image, the kernels without LDS gathers; tests)
+    int merge_off32 = 1;              // read at launch: cold gathers through a 32-bit byte offset from the vector's
+                                      // base when the vector is at most 4 GiB (0: 64-bit addresses always; tests)
     int merge_pack = 1;               // build time: band entries packed in 20/24 bits when the vector allows
                                       // (0: 32 bits, 24: at least 24; tests)
 };

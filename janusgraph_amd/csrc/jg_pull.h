@@ -315,47 +315,102 @@ struct HotSegs {
 // the column restored from loc: line = g << bits | (h ^ the hash bits of the group's first line).
 // MSEG = false: the vector is one segment (every one-shard plan).  All of a band's groups are below
 // 2^sb then (g < 2^(31 - gshift)), so seg = 0, j = g and the LDS index of a hot entry is loc itself.
-template <class Op, bool MSEG = true>
+// O32 = true: the vector is at most 4 GiB (launch_pull's gate).  An entry is then held byte-scaled,
+// e = loc * sizeof(T) (unpack_entry shifts while it unpacks), so that e is the hot entry's LDS byte
+// address as it stands and a cold entry is loaded from the uniform base vec() plus a 32-bit byte
+// offset built from e: no 64-bit address arithmetic per gather.  O32 = false: e = loc, element indices
+// and 64-bit addresses (Op::gather).  FULL = true (the task has all kMergeTask entries: every task of a
+// sub-slice but its last) drops the per-entry validity tests.
+template <class Op, bool MSEG = true, bool O32 = false>
 struct SliceGather {
     using T = typename Op::T;
+    static constexpr int LG = sizeof(T) == 4 ? 2 : sizeof(T) == 8 ? 3 : 4;
+    static_assert(sizeof(T) == (1u << LG), "4-, 8- or 16-byte values");
+    static constexpr int SH = O32 ? LG : 0;  // e = loc << SH
     const Op& op;
     lds_ptr<const T> lds;
     uint32_t hg;        // hot line groups per segment
     int sb;             // tbits - gshift: group bits inside a segment
     int bits;
     uint32_t hmask, h;  // 2^bits - 1, the sub-slice
-    uint32_t idcell;    // the identity cell just past the staged lines
-    __device__ __forceinline__ bool is_hot(uint32_t loc) const {
-        if constexpr (!MSEG) return loc < (hg << 4);
-        return ((loc >> 4) & ((1u << sb) - 1u)) < hg;
+    uint32_t idcell;    // the identity cell just past the staged lines, scaled like an entry (<< SH)
+    __device__ __forceinline__ T lds_at(uint32_t e) const {
+        if constexpr (O32) return *(lds_ptr<const T>)((lds_ptr<const unsigned char>)lds + e);
+        return lds[e];
+    }
+    __device__ __forceinline__ bool is_hot(uint32_t e) const {
+        if constexpr (!MSEG) return e < idcell;  // one segment: idcell = hg << (4 + SH)
+        return ((e >> (4 + SH)) & ((1u << sb) - 1u)) < hg;
     }
     // Cold and invalid lanes read the identity cell: no select, so the read cannot become a branch.
-    __device__ __forceinline__ T hot(uint32_t loc, bool valid) const {
-        if constexpr (!MSEG) return lds[valid && loc < (hg << 4) ? loc : idcell];
-        const uint32_t g = loc >> 4, j = g & ((1u << sb) - 1u), seg = g >> sb;
-        return lds[valid && j < hg ? (((seg * hg + j) << 4) | (loc & 15u)) : idcell];
+    // One segment: the hot entries are exactly those below the identity cell, so the index is a clamp.
+    template <bool FULL>
+    __device__ __forceinline__ T hot(uint32_t e, bool valid) const {
+        if constexpr (!MSEG) {
+            const uint32_t i = min(e, idcell);
+            if constexpr (FULL) return lds_at(i);
+            return lds_at(valid ? i : idcell);
+        }
+        const uint32_t g = e >> (4 + SH), j = g & ((1u << sb) - 1u), seg = g >> sb;
+        const bool take = FULL ? j < hg : valid && j < hg;
+        return lds_at(take ? (((seg * hg + j) << (4 + SH)) | (e & (15u << SH))) : idcell);
     }
-    __device__ __forceinline__ int32_t col(uint32_t loc) const {
-        const uint32_t x = (loc >> 4) << bits;  // the group's first line
+    // the vector line of the entry's group in this sub-slice
+    __device__ __forceinline__ uint32_t line(uint32_t e) const {
+        const uint32_t x = (e >> (4 + SH)) << bits;  // the group's first line
         const uint32_t hx = (x ^ (x >> 8) ^ (x >> 16) ^ (x >> 24)) & hmask;
-        return (int32_t)(((x | (h ^ hx)) << 4) | (loc & 15u));
+        return x | (h ^ hx);
+    }
+    __device__ __forceinline__ T load(uint32_t e) const {
+        if constexpr (O32) {
+            const uint32_t off = (line(e) << (4 + LG)) | (e & (15u << LG));
+            return *reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(op.vec()) + off);
+        }
+        return op.gather((int32_t)((line(e) << 4) | (e & 15u)));
     }
     // Only valid cold lanes load (exec-masked); the others keep identity().
-    __device__ __forceinline__ T cold(uint32_t loc, bool valid, bool lds_on) const {
+    template <bool FULL>
+    __device__ __forceinline__ T cold(uint32_t e, bool valid, bool lds_on) const {
+        if constexpr (FULL) {
+            if (!lds_on) return load(e);
+        }
         T v = op.identity();
-        if (valid && !(lds_on && is_hot(loc))) v = op.gather(col(loc));
+        const bool c = !(lds_on && is_hot(e));
+        if (FULL ? c : valid && c) v = load(e);
         return v;
     }
 };
 
-// Entry u of a lane chunk packed in W bits (bit stream over the chunk's dwords).
-template <int W>
+// Entry u of a lane chunk packed in W bits (bit stream over the chunk's dwords), shifted left by SH:
+// the shift is folded into the unpack's own shift and mask.
+template <int W, int SH = 0>
 __device__ __forceinline__ uint32_t unpack_entry(const uint32_t (&d)[W / 4], int u) {
     const int o = W * u, i = o >> 5, sh = o & 31;
-    uint32_t v = d[i] >> sh;
-    if (sh + W > 32) v |= d[i + 1] << (32 - sh);
-    if constexpr (W < 32) v &= (1u << W) - 1u;
+    static_assert(W + SH <= 32 || W == 32, "a scaled entry fits a dword (W = 32: by launch_pull's gate)");
+    uint32_t v;
+    if (sh >= SH) {
+        v = d[i] >> (sh - SH);
+        if (sh + W > 32) v |= d[i + 1] << (32 - sh + SH);
+    } else {
+        v = d[i] << (SH - sh);  // sh + W <= 32 here: W <= 32 - SH, or W = 32 and sh = 0
+    }
+    if constexpr (W < 32) v &= ((1u << W) - 1u) << SH;
     return v;
+}
+
+// A value that is the same in every lane of the wave, moved to scalar registers.
+__device__ __forceinline__ int uniform32(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ int64_t uniform64(int64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// a < b for wave-uniform values whose difference cannot overflow, as a test of the difference's sign
+// word: the scalar unit compares 64-bit values for equality only, and a plain a < b goes to the vector
+// unit (readfirstlane of a scalar is a copy; it keeps the compiler from forming a < b again).
+__device__ __forceinline__ bool uniform_less64(int64_t a, int64_t b) {
+    return __builtin_amdgcn_readfirstlane((int)((uint64_t)(a - b) >> 32)) < 0;
 }
 
 // The value of lane (lane - d) mod 64, dword by dword.
@@ -382,7 +437,8 @@ struct op_task_live : std::false_type {};
 template <class Op>
 struct op_task_live<Op, std::void_t<decltype(Op::kTaskLive)>> : std::bool_constant<Op::kTaskLive> {};
 
-template <class Op, bool LDS, int PW, bool MSEG = false>
+// O32: the vector is at most 4 GiB, entries are unpacked byte-scaled (SliceGather).
+template <class Op, bool LDS, int PW, bool MSEG = false, bool O32 = false>
 __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, Op op, typename Op::T* __restrict__ partial,
                                                                    typename Op::T* __restrict__ carry, HotSegs hs,
                                                                    int temporal) {
@@ -416,10 +472,13 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
         return (grp << a.bits) + (int64_t)(hh ^ (sub_hash(grp << gshift) & hmask));
     };
     for (int rd = 0; rd < rounds; ++rd) {
-    const int h = (xcd % xs) | ((temporal ? rd : w % per) << 3);
+    // (Block-uniform, but the divisions run on the vector unit: uniform32/64 move their results, and
+    // with them the sub-slice's bounds and every task index, to scalar registers, so the task loop's
+    // index and address arithmetic runs on the scalar unit.)
+    const int h = uniform32((xcd % xs) | ((temporal ? rd : w % per) << 3));
     // this block's rank among h's blocks
     const int64_t g = (int64_t)(temporal ? w : w / per) * rep + xcd / xs;
-    const int64_t G = (int64_t)(temporal ? W : W / per) * rep;
+    const int64_t G = uniform64((int64_t)(temporal ? W : W / per) * rep);
     if constexpr (LDS) {
         if (rd > 0) __syncthreads();  // every wave is done with the previous round's image
         // LDS line i = the line of sub-slice h in hot line group i (a permutation of each aligned group).
@@ -460,11 +519,12 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
         }
         __syncthreads();
     }
-    const SliceGather<Op, MSEG> lg{op,       hotv, (uint32_t)hg, hs.tbits - gshift, a.bits, (1u << a.bits) - 1u, (uint32_t)h,
-                             (uint32_t)nl * 16u};
-    const int64_t base = a.sub_base[h];
-    const int64_t ntask = a.sub_base[h + 1] - base;
-    const int64_t hbegin = a.sub_begin[h], hend = a.sub_end[h];
+    using Gather = SliceGather<Op, MSEG, O32>;
+    const Gather lg{op, hotv, (uint32_t)hg, hs.tbits - gshift, a.bits, (1u << a.bits) - 1u, (uint32_t)h,
+                    ((uint32_t)nl * 16u) << Gather::SH};
+    const int64_t base = uniform64(a.sub_base[h]);
+    const int64_t ntask = uniform64(a.sub_base[h + 1]) - base;
+    const int64_t hbegin = uniform64(a.sub_begin[h]), hend = uniform64(a.sub_end[h]);
     // The block's j-th task, j = 0, 1, ...: interleaved, k = j * G + (g + rd) mod G, so the G blocks of
     // a sub-slice differ by at most one task per round and the rotation spreads the extra tasks over
     // the blocks round by round (chunks of 16 per block gave the low blocks up to one more chunk in
@@ -473,7 +533,7 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
     // cheaper tasks takes more and the round's barrier waits less for the slowest wave (RMAT-24 0.848
     // -> 0.800 ms).  Any order gives the same result (tasks are independent).
     constexpr bool dyn = LDS;
-    const int64_t grot = (g + rd) % G;
+    const int64_t grot = uniform64((g + rd) % G);
     auto task_of = [&](int64_t j) { return j * G + grot; };
     auto grab = [&]() -> int64_t {
         uint32_t j = 0;
@@ -484,7 +544,7 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
     auto advance = [&]() -> int64_t {
         if (dyn) return grab();
         jstat += kMergeWaves;
-        return task_of(jstat);
+        return uniform64(task_of(jstat));
     };
     // a skipped task (a.live): a scalar load of its bit (waiting on it does not wait for the vector
     // gathers in flight), then the next task
@@ -495,7 +555,7 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
         const uint32_t wd = __builtin_amdgcn_readfirstlane(a.live[tt >> 5]);
         return ((wd >> (tt & 31)) & 1u) == 0;
     };
-    int64_t k = dyn ? grab() : task_of(jstat);
+    int64_t k = dyn ? grab() : uniform64(task_of(jstat));
     while (dead(k)) k = advance();
     if (k >= ntask) continue;
     // The next task's entries and metadata are loaded while this task's gathers are in flight.  The
@@ -505,60 +565,73 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
     // scalar prefetch would hold up every LDS wait (lgkmcnt does not count SMEM in order).
     static_assert(kMergeEpl == 8, "a lane chunk is 8 entries");
     constexpr int DB = PW / 4 - 4;  // dwords of a chunk in pack_b
-    auto chunk = [&](int64_t kk) { return (hbegin >> 3) + kk * kWave + lane; };
-    auto meta_idx = [&](int64_t kk) { return 2 * (base + kk) + (lane & 1); };
-    auto head_idx = [&](int64_t kk) { return (base + kk) * kWave + lane; };
-    auto ld = [](const auto* p) { return *p; };
+    // a task's first chunk, head byte and meta word: uniform, so that a load's address is a scalar
+    // base plus the lane's constant 32-bit offset
+    auto chunk0 = [&](int64_t kk) { return (hbegin >> 3) + kk * kWave; };
+    auto meta0 = [&](int64_t kk) { return 2 * (base + kk); };
+    auto head0 = [&](int64_t kk) { return (base + kk) * kWave; };
+    const uint32_t ulane = (uint32_t)lane;
     using v4u = uint32_t __attribute__((ext_vector_type(4)));
     using v2u = uint32_t __attribute__((ext_vector_type(2)));
     auto load_chunk = [&](int64_t kk, uint32_t (&d)[PW / 4]) {
-        const int64_t x = chunk(kk);
-        const v4u va = ld(reinterpret_cast<const v4u*>(a.pack_a) + x);
+        const int64_t x = chunk0(kk);
+        const v4u va = (reinterpret_cast<const v4u*>(a.pack_a) + x)[ulane];
         d[0] = va.x, d[1] = va.y, d[2] = va.z, d[3] = va.w;
         if constexpr (DB == 1) {
-            d[4] = ld(a.pack_b + x);
+            d[4] = (a.pack_b + x)[ulane];
         } else if constexpr (DB == 2) {
-            const v2u vb = ld(reinterpret_cast<const v2u*>(a.pack_b) + x);
+            const v2u vb = (reinterpret_cast<const v2u*>(a.pack_b) + x)[ulane];
             d[4] = vb.x, d[5] = vb.y;
         } else {
-            const v4u vb = ld(reinterpret_cast<const v4u*>(a.pack_b) + x);
+            const v4u vb = (reinterpret_cast<const v4u*>(a.pack_b) + x)[ulane];
             d[4] = vb.x, d[5] = vb.y, d[6] = vb.z, d[7] = vb.w;
         }
     };
+    auto load_head = [&](int64_t kk) -> uint32_t { return (a.heads + head0(kk))[ulane]; };
+    auto load_meta = [&](int64_t kk) -> int32_t { return (a.meta + meta0(kk))[ulane & 1u]; };
     uint32_t cd[PW / 4];
     load_chunk(k, cd);
-    uint32_t hb = ld(a.heads + head_idx(k));
-    int32_t mw = ld(a.meta + meta_idx(k));
-    for (;;) {
+    uint32_t hb = load_head(k);
+    int32_t mw = load_meta(k);
+    int64_t kn = k;
+    // One task, compiled twice: FULL (all kMergeTask entries: every task of a sub-slice but its last)
+    // has no per-entry validity tests, knows that every lane holds entries and that the task's last
+    // segment ends in lane 63; the other body is the sub-slice's last, partial task.  Both are the same
+    // sums in the same order.
+    auto run_task = [&](auto full_c) __attribute__((always_inline)) {
+        constexpr bool FULL = decltype(full_c)::value;
         const int64_t t = base + k;
-        const int64_t e0 = hbegin + k * kMergeTask;
-        const int n = (int)min((int64_t)kMergeTask, hend - e0);
-        uint32_t loc[kMergeEpl];
+        const int n = FULL ? kMergeTask : (int)(hend - (hbegin + k * kMergeTask));
+        uint32_t loc[kMergeEpl];  // scaled entries (SliceGather: loc << SH)
 #pragma unroll
-        for (int u = 0; u < kMergeEpl; ++u) loc[u] = unpack_entry<PW>(cd, u);
+        for (int u = 0; u < kMergeEpl; ++u) loc[u] = unpack_entry<PW, Gather::SH>(cd, u);
         const int32_t j0 = __builtin_amdgcn_readlane(mw, 0);
         const bool carry_in = __builtin_amdgcn_readlane(mw, 1) != 0;
         const uint32_t hbc = hb;
-        T v[kMergeEpl];
+        T v[kMergeEpl], vl[kMergeEpl];
         if constexpr (LDS) {
-            T vg[kMergeEpl], vl[kMergeEpl];
 #pragma unroll
-            for (int u = 0; u < kMergeEpl; ++u) vl[u] = lg.hot(loc[u], kMergeEpl * lane + u < n);
-#pragma unroll
-            for (int u = 0; u < kMergeEpl; ++u) vg[u] = lg.cold(loc[u], kMergeEpl * lane + u < n, true);
-#pragma unroll
-            for (int u = 0; u < kMergeEpl; ++u) v[u] = op.combine(vl[u], vg[u]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < kMergeEpl; ++u) v[u] = lg.cold(loc[u], kMergeEpl * lane + u < n, false);
+            for (int u = 0; u < kMergeEpl; ++u) vl[u] = lg.template hot<FULL>(loc[u], kMergeEpl * lane + u < n);
         }
-        int64_t kn = advance();
+#pragma unroll
+        for (int u = 0; u < kMergeEpl; ++u) v[u] = lg.template cold<FULL>(loc[u], kMergeEpl * lane + u < n, LDS);
+        kn = advance();
         while (dead(kn)) kn = advance();
-        if (kn < ntask) {
-            load_chunk(kn, cd);
-            hb = ld(a.heads + head_idx(kn));
-            mw = ld(a.meta + meta_idx(kn));
+        {
+            // unconditional, the task index clamped as in load_cols: past the last task the loads
+            // re-read it (nobody uses them), and the wait for the gathers above stays a counted one
+            // instead of waiting for these loads as well
+            const int64_t kc = uniform_less64(kn, ntask) ? kn : ntask - 1;
+            load_chunk(kc, cd);
+            hb = load_head(kc);
+            mw = load_meta(kc);
         }
+        // Two scheduling fences keep this order: the prefetch is issued before anything waits for the
+        // gathers, and the first use of a gathered value (the combine below) comes after the head
+        // numbers, which need no memory.  (Left to itself the scheduler put the combines, and with them
+        // a wait for every gather, in front of the prefetch.  RMAT-24, alternating runs: with the
+        // fences 0.6870-0.6879 ms, without 0.6891-0.6913; profiles/r08/merge_gather/.)
+        __builtin_amdgcn_sched_barrier(0);
         // head numbers without a cross-lane scan: ballot b holds the lanes whose head count (0..8) has
         // bit b set, so the heads in the lanes below this one are the sum over b of 2^b times the
         // ballot's bits below it (mbcnt), and the task's heads the same sum of the ballots' popcounts
@@ -574,7 +647,14 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
             hbase += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u)) << b;
             H += __builtin_popcountll(cb) << b;
         }
-        const bool valid_lane = kMergeEpl * lane < n;
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (LDS) {
+#pragma unroll
+            for (int u = 0; u < kMergeEpl; ++u) v[u] = op.combine(vl[u], v[u]);
+        }
+        const bool valid_lane = FULL || kMergeEpl * lane < n;
+        // the task's last segment ends in this lane
+        const bool last_lane = FULL ? lane == kWave - 1 : valid_lane && kMergeEpl * (lane + 1) >= n;
         // A task's partials are consecutive slots: with at most `stage` heads they are collected in the
         // wave's LDS window and written by one coalesced store per 64, instead of up to 10 exec-masked
         // scattered stores per lane (the stores cost ~20% of the merge kernel, round 2).
@@ -638,7 +718,7 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
             const T in_x = scan_in(fh < kMergeEpl ? run : pre);
             if (valid_lane) {
                 if (lane > 0 && fh < kMergeEpl) emit(in_h, fh > 0 ? op.combine(in_x, pre) : in_x);
-                if (kMergeEpl * (lane + 1) >= n) {  // the task's last segment ends here
+                if (last_lane) {  // the task's last segment ends here
                     if (fh < kMergeEpl) emit(run_h, run);
                     else emit(in_h, lane > 0 ? op.combine(in_x, pre) : pre);
                 }
@@ -670,9 +750,8 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
             // the segment that entered from the left ends at this lane's first head
             stg[valid_lane && lane > 0 && seen ? in_h : dump] = (hbc & 1u) ? in_x : joined;
             // the task's last segment ends in its last lane
-            const bool last = valid_lane && kMergeEpl * (lane + 1) >= n;
             const T whole = lane > 0 ? joined : pre;
-            stg[last ? (seen ? slot : in_h) : dump] = seen ? acc : whole;
+            stg[last_lane ? (seen ? slot : in_h) : dump] = seen ? acc : whole;
             // the window is wave-private and LDS runs a wave's instructions in order: the fences only
             // keep the compiler from moving these reads above the writes (or the next task's writes
             // above these reads)
@@ -694,7 +773,13 @@ __global__ __launch_bounds__(kMergeThreads) void pull_merge_kernel(MergeArgs a, 
         } else {
             fold_direct();
         }
-        if (kn >= ntask) break;
+    };
+    for (;;) {
+        // decided on the scalar unit: k, hbegin and hend are the same in every lane
+        const bool full = !uniform_less64(hend - (hbegin + k * kMergeTask), kMergeTask);
+        if (__builtin_expect(full, 1)) run_task(std::true_type{});
+        else run_task(std::false_type{});
+        if (!uniform_less64(kn, ntask)) break;
         k = kn;
     }
     }  // rounds
@@ -855,20 +940,28 @@ void launch_pull(const Csr& csr, const PullPlan& plan, const Op& op, typename Op
     // a side stream beside band 0's, two merge workgroups per CU with half the LDS image each, the light
     // rows through a persistent LDS-prefix kernel: no gain or slower at RMAT-24 and 26)
     if (split) {
+        // the merge kernel of a band: its entry width, then (LDS image, segments, 32-bit offsets)
+        auto with_kernel = [](int width, bool image, bool mseg, bool o32, auto&& f) {
+            auto widths = [&](auto l, auto m, auto o) {
+                constexpr bool L = decltype(l)::value, M = decltype(m)::value, O = decltype(o)::value;
+                if (width == 20) f(pull_merge_kernel<Op, L, 20, M, O>);
+                else if (width == 24) f(pull_merge_kernel<Op, L, 24, M, O>);
+                else f(pull_merge_kernel<Op, L, 32, M, O>);
+            };
+            constexpr std::true_type yes{};
+            constexpr std::false_type no{};
+            if (image && mseg) o32 ? widths(yes, yes, yes) : widths(yes, yes, no);
+            else if (image) o32 ? widths(yes, no, yes) : widths(yes, no, no);
+            else o32 ? widths(no, no, yes) : widths(no, no, no);
+        };
         static bool attr = false;
         if (!attr) {
-            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 20>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
-            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 24>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
-            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 32>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
-            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 20, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
-            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 24, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
-            JG_HIP(hipFuncSetAttribute((const void*)pull_merge_kernel<Op, true, 32, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMergeLdsBytes));
+            for (int width : {20, 24, 32})
+                for (int v = 0; v < 4; ++v)
+                    with_kernel(width, true, (v & 1) != 0, (v & 2) != 0, [](auto kern) {
+                        JG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   kMergeLdsBytes));
+                    });
             attr = true;
         }
         for (size_t bi = band0; bi < plan.bands.size(); ++bi) {
@@ -902,23 +995,15 @@ void launch_pull(const Csr& csr, const PullPlan& plan, const Op& op, typename Op
             hs.tbits = plan.seg_tbits;
             hs.nseg = plan.nseg;
             const int64_t seg_cap = plan.nseg == 1 ? plan.col_space : (1ll << plan.seg_tbits) - gsz;
-            hs.hs = plan.lds_ok ? (int32_t)(std::min<int64_t>(hot_max / plan.nseg, seg_cap) / gsz * gsz) : 0;
+            int64_t hot = plan.lds_ok ? std::min<int64_t>(hot_max / plan.nseg, seg_cap) : 0;
+            if (tune().merge_hot >= 0) hot = std::min<int64_t>(hot, tune().merge_hot);
+            hs.hs = (int32_t)(hot / gsz * gsz);
+            // 32-bit byte offsets from vec() when they reach the whole vector
+            const bool o32 = tune().merge_off32 != 0 && plan.col_space * (int64_t)sizeof(T) <= (1ll << 32);
             const int temporal = tune().merge_temporal == 2 || (tune().merge_temporal == 1 && plan.temporal);
             const size_t lds = hs.hs > 0 ? (size_t)(hs.nseg * (hs.hs / S) + 1) * sizeof(T) + (size_t)stage_bytes + 16 : 0;
             auto go = [&](auto kern) { kern<<<grid, kMergeThreads, lds, s>>>(ma, op, part, carry, hs, temporal); };
-            if (hs.hs > 0 && hs.nseg > 1) {
-                if (bd.width == 20) go(pull_merge_kernel<Op, true, 20, true>);
-                else if (bd.width == 24) go(pull_merge_kernel<Op, true, 24, true>);
-                else go(pull_merge_kernel<Op, true, 32, true>);
-            } else if (hs.hs > 0) {
-                if (bd.width == 20) go(pull_merge_kernel<Op, true, 20>);
-                else if (bd.width == 24) go(pull_merge_kernel<Op, true, 24>);
-                else go(pull_merge_kernel<Op, true, 32>);
-            } else {
-                if (bd.width == 20) go(pull_merge_kernel<Op, false, 20>);
-                else if (bd.width == 24) go(pull_merge_kernel<Op, false, 24>);
-                else go(pull_merge_kernel<Op, false, 32>);
-            }
+            with_kernel(bd.width, hs.hs > 0, hs.nseg > 1, o32, go);
             JG_LAUNCH_CHECK();
         }
         FixupBands fx{};
