@@ -1071,8 +1071,10 @@ void build_pull_plan(Shard& sh, const Csr& csr, PullPlan& plan, int64_t col_spac
     if (debug_plan()) {
         std::vector<int64_t> rp(rows + 1);
         copy_d2h(rp.data(), csr.row_ptr.get(), (rows + 1) * sizeof(int64_t), s);
-        std::fprintf(stderr, "[jg plan] shard %d rows %lld nnz %lld hubs %lld chunks %lld\n", sh.index, (long long)rows,
-                     (long long)csr.nnz, (long long)plan.num_hub_rows, (long long)plan.num_chunks);
+        const char* adj = &plan == &sh.plan_in ? "IN" : &plan == &sh.plan_out ? "OUT" : &plan == &sh.plan_both ? "BOTH" : "?";
+        std::fprintf(stderr, "[jg plan] shard %d adj %s rows %lld nnz %lld hubs %lld chunks %lld split_rows %lld max_hub_row %lld\n",
+                     sh.index, adj, (long long)rows, (long long)csr.nnz, (long long)plan.num_hub_rows,
+                     (long long)plan.num_chunks, (long long)plan.split_rows, (long long)plan.max_hub_row);
         for (int c = 1; c < kNumClasses; ++c) {
             const int64_t b = plan.class_row_begin[c], e = plan.class_row_end[c];
             std::fprintf(stderr, "[jg plan]   class %d lanes %2d rows [%lld,%lld) = %lld nnz %lld blocks %lld\n", c,
@@ -1085,6 +1087,19 @@ void build_pull_plan(Shard& sh, const Csr& csr, PullPlan& plan, int64_t col_spac
                          bd.bits, (long long)bd.row_begin, (long long)bd.row_end,
                          (long long)(rp[bd.row_end] - rp[bd.row_begin]), (long long)bd.subrows, (long long)bd.tasks);
         }
+        // the class table of the rows after the split (equal to the one above without bands)
+        for (int c = 1; c < kNumClasses; ++c) {
+            const int64_t b = plan.light_row_begin[c], e = plan.light_row_end[c];
+            std::fprintf(stderr, "[jg plan]   light %d lanes %2d rows [%lld,%lld) = %lld nnz %lld blocks %lld\n", c,
+                         64 >> (c - 1), (long long)b, (long long)e, (long long)(e - b), (long long)(rp[e] - rp[b]),
+                         (long long)(plan.light_block_begin[c + 1] - plan.light_block_begin[c]));
+        }
+        std::fprintf(stderr, "[jg plan]   runs %d", plan.runs ? 1 : 0);
+        if (plan.runs) {
+            std::fprintf(stderr, " run_begin");
+            for (int d = 1; d <= kRunMax; ++d) std::fprintf(stderr, " %lld", (long long)plan.run_begin[d]);
+        }
+        std::fprintf(stderr, "\n");
     }
 }
 
