@@ -1,5 +1,5 @@
 // jg_frontier.h — frontier queues, and the walk over their edges, shared by the traversals
-// (jg_traverse.hip, jg_narrow.hip) and CC (jg_cc.hip).
+// (jg_traverse.hip, jg_narrow.hip), shortest distance (jg_sssp.hip) and CC (jg_cc.hip).
 #pragma once
 
 #include "jg_prim.h"
@@ -130,6 +130,21 @@ struct WaveApp {
     }
     __device__ void final(int32_t* q, int64_t* qo, unsigned long long* packed) { wave_stage_final(sa, run, q, qo, packed); }
 };
+
+// Append v to a plain queue (no edge offsets): one ballot and one atomicAdd per wave.  Must be reached by
+// all 64 lanes (wave-uniform call sites).
+__device__ __forceinline__ void wave_append(bool take, int32_t v, int32_t* __restrict__ queue,
+                                            unsigned long long* __restrict__ size) {
+    const uint64_t mask = __ballot(take);
+    if (mask == 0) return;
+    const int leader = __ffsll((unsigned long long)mask) - 1;
+    unsigned long long base = 0;
+    if (lane_id() == leader) base = atomicAdd(size, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader, kWave);
+    if (take) queue[base + __popcll(mask & lanemask_lt())] = v;
+}
+
+constexpr int kTdEdgesPerThread = 4;  // consecutive frontier edges a thread takes after one seek
 
 // Edge-parallel walk over a frontier.  A queue of nq entries carries each entry's first edge number
 // (qoff, monotone; mf edges in all), so frontier edge e in [0, mf) belongs to the entry i with

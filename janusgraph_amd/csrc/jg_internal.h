@@ -611,6 +611,12 @@ int cc_root_eccentricity(Ctx& ctx, Shard& sh, const CcRoots& r, int32_t* depth, 
 // Sharded (halo plans, every shard of the process): the same from the rows whose label (r.parent) is
 // their rank, r.minr unused, one CcRoots per local shard; -1 if no vertex has an edge (jg_traverse.hip).
 int cc_root_eccentricity_sharded(Graph& g, const CcRoots* roots, double* edges_out);
+// One shard: the hop depths (device, [rows], -1 unreached) from local row `seed` along IN edges, capped at
+// max_depth, by the DO-BFS (pulling over OUT when present), for unit-weight shortest distance (jg_sssp.hip);
+// end_ev is recorded behind the last level batch.  Returns the levels run (jg_traverse.hip).
+int bfs_in_depths(Ctx& ctx, Shard& sh, int64_t seed, int max_depth, int32_t* depth, hipEvent_t end_ev);
+// The owning shard (*shard_out, left alone when absent) and local row of a caller vid; -1: not a vertex
+int64_t local_of_vid(const Graph& g, int64_t vid, int* shard_out);
 // Allocate the single-shard traversal's scratch (no-op when present; jg_traverse.hip).
 void bfs_buffers(Shard& sh);
 // Csr::first_col of a traversal's pull adjacency (built on first use, on the shard's stream)

@@ -255,7 +255,7 @@ def test_three_rank_gloo_halo_exchange(oracle_lib):
 
 
 def _sd_worker(rank, ws, port, out_q):
-    """Sharded ShortestDistanceVertexProgram (jg_traverse.hip shortest_distance_sharded) modelled rank
+    """Sharded ShortestDistanceVertexProgram (jg_sssp.hip shortest_distance_sharded) modelled rank
     by rank over gloo: the IN adjacency's halo layout as in _halo_worker; per superstep each rank
     pushes min(msg[w] + weight) from its frontier rows into own rows and halo slots, the REVERSE
     halo exchange (exchange_halo_reverse: segment for peer q goes back to q, landing at q's send-list

@@ -1,4 +1,4 @@
-"""Weighted ShortestDistance with an unbounded hop count: near-far delta-stepping (jg_traverse.hip
+"""Weighted ShortestDistance with an unbounded hop count: near-far delta-stepping (jg_sssp.hip
 sd_delta_stepping) against the oracle's superstep restatement
 (oracle/jg_oracle.c jo_shortest_distance, ShortestDistanceVertexProgram.java:112-146), bit for bit.
 
@@ -196,6 +196,55 @@ def test_delta_stepping_rmat20_matches_oracle(ctx, oracle_lib, delta, dist32):
     assert (want >= 0).sum() > n // 4  # most of the graph reached
     assert ctx.stats()["levels"] > 1
     g.close()
+
+
+@pytest.fixture(scope="module")
+def rmat14_bounded(oracle_lib):
+    """RMAT-14, edge factor 16, weights 1..30, seeded at the row of largest in-degree, maxDepth = 6: the
+    oracle's distances and its hop depths along the direction the distances travel (computed once)."""
+    o = oracle_lib
+    n = 1 << 14
+    s, t = o.rmat_edges(14, 16, 14)
+    s, t = s.astype(np.int32), t.astype(np.int32)
+    w = np.random.default_rng(14).integers(1, 31, len(s)).astype(np.int32)
+    vid = (np.random.default_rng(15).permutation(n).astype(np.int64) + 1) << 8
+    in_len = np.bincount(t, minlength=n)  # row x's IN adjacency row: the edges u -> x
+    seed = int(in_len.argmax())
+    want = o.shortest_distance(n, s, t, seed, 6, w)
+    # an edge u -> x carries x's distance to u (test_hop_bound_gate): the hops run against the edges
+    hops = o.bfs(n, s, t, seed, o.DIR_IN, 6).astype(np.int64)
+    return n, vid, s, t, w, seed, want, hops, in_len
+
+
+@pytest.mark.parametrize("shards", [1, 3])
+def test_superstep_push_crosses_tiles(ctx, rmat14_bounded, shards):
+    """The hop-bounded supersteps on a frontier longer than one tile of the single-shard push, against the
+    oracle bit for bit, on one shard and on three (halo plan).  maxDepth = 6 << rows - 1, so the supersteps
+    run whatever sd_delta is.
+
+    The tile: the IN adjacency has 16 * 2^14 = 262,144 entries, so the push grid is
+    max(262,144 / (256 threads * 4 edges * 4), 64) = 64 workgroups, and one tile of its loop is 64 workgroups
+    * 256 threads * 4 edges per thread = 65,536 edges; a longer frontier takes the loop round again and
+    lets its workgroups leave at different tiles.  That the case has such a frontier follows from the
+    oracle alone: a row first reached at hop depth d is in superstep d + 1's frontier, which therefore
+    holds at least the IN rows of all rows at depth d; some depth d < 6 must sum them past 65,536."""
+    import janusgraph_amd as jg
+    n, vid, s, t, w, seed, want, hops, in_len = rmat14_bounded
+    assert np.array_equal(hops >= 0, want != jg.DIST_ABSENT)  # the depths run the way the distances do
+    frontier_edges = [int(in_len[hops == d].sum()) for d in range(6)]
+    print("frontier edges by hop depth:", frontier_edges)
+    assert max(frontier_edges) > 64 * 256 * 4
+    c = ctx if shards == 1 else jg.Context((0,) * shards)
+    try:
+        jg._lib.tune_set("halo", 1)
+        g = c.build(vid, vid[s], vid[t], weight=w, flags=jg.ADJ_IN)
+        got = run_sd(g, vid[seed], 6, -1)
+        np.testing.assert_array_equal(got, want)
+        assert (got > 0).sum() > n // 4
+        g.close()
+    finally:
+        if c is not ctx:
+            c.close()
 
 
 @pytest.mark.parametrize("wpath", [0, 1, 5])

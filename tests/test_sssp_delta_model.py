@@ -1,4 +1,4 @@
-"""CPU model of the near-far delta-stepping step discipline (jg_traverse.hip sd_delta_stepping_t,
+"""CPU model of the near-far delta-stepping step discipline (jg_sssp.hip sd_delta_stepping_t,
 sd_decide, sd_split_kernel, sd_near_kernel: the passes controlled on the device, round 6) against the
 oracle's supersteps (oracle/jg_oracle.c jo_shortest_distance), no GPU: each step relaxes its near queue
 when that has entries, else stops when the far pile is empty, else moves the far pile with the threshold
