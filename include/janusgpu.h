@@ -38,6 +38,9 @@
  *   jg_connected_components
  *       TinkerPop ConnectedComponentVertexProgram (String-min label over BOTH edges,
  *       VertexProgramScanJob.java:113-135 loads BOTH); pinned by OLAPTest.java:736-762
+ *   jg_peer_pressure
+ *       TinkerPop PeerPressureVertexProgram (weighted mode of the neighbours' cluster votes over outE or
+ *       bothE, optional vote distribution), under the same loop; ties go to the smallest cluster id
  *   jg_combine_steps
  *       the same loop for sum/min/max MessageCombiner programs (OLAPTest.DegreeCounter,
  *       janusgraph-test/.../olap/OLAPTest.java:424-503; VertexState.java:85-114)
@@ -67,7 +70,8 @@ extern "C" {
  * jg_abi_version() == JG_ABI_VERSION before passing any struct across the ABI.
  * Still 3 (entry points only, no layout change): jg_builder_keep_labels, jg_builder_add_labeled_edges,
  * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added; jg_cc_census, jg_cc_census_read,
- * jg_cc_census_release added; jg_pagerank_top, jg_pagerank_top_read, jg_pagerank_top_release added. */
+ * jg_cc_census_release added; jg_pagerank_top, jg_pagerank_top_read, jg_pagerank_top_release added;
+ * jg_peer_pressure added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -475,6 +479,41 @@ int jg_cc_census_read(jg_graph* g, int64_t first, int64_t count, int64_t* compon
                       int64_t* population_out);
 /* Drops the held census (JG_OK when none is held). */
 int jg_cc_census_release(jg_graph* g);
+
+/* PeerPressureVertexProgram (TinkerPop 3.4.6, g.V().peerPressure(); third party, recalled): every vertex
+ * starts in its own cluster (cluster id = its vertex id) and repeatedly joins the cluster that its neighbours
+ * vote for most strongly.  cluster_vid_out[n] (caller order, nullable) = the id of each vertex's cluster.
+ *   direction = the edges of the vote scope.  JG_DIR_OUT (the program's default, outE): a vertex votes along its
+ *     out-edges, so vertex v receives one vote per entry of its IN adjacency row (the pull of
+ *     VertexMemoryHandler.java:121-151; multi-edges count once per edge).  JG_DIR_BOTH (bothE): v receives one
+ *     vote per entry of its BOTH row (a self-loop appears twice).
+ *   Strength: distribute_vote == 0: every vote weighs 1.  distribute_vote != 0: the vote of u weighs
+ *     1.0 / (number of entries in which u is the sender) as an IEEE double: u's out-degree under JG_DIR_OUT, the
+ *     length of its BOTH row under JG_DIR_BOTH; a vertex that is the sender of no entry has strength +Inf, sends
+ *     nothing and never leaves its own cluster.
+ *   Vote superstep (synchronous: every read is of the previous superstep): votes = {cluster[v]: strength[v]},
+ *     then votes[cluster[u]] += strength[u] for every entry u of v's row; v's new cluster is the one with the
+ *     largest sum.  Sums are fp64; the order of the additions inside one sum is unspecified, but the result is
+ *     the same on every run over the same graph.
+ *   Tie rule (this library's own): among clusters with exactly equal sums the numerically smallest cluster id
+ *     (signed int64) wins.  Fulgora's choice in a tie follows HashMap iteration order and message arrival order;
+ *     no caller can rely on it.
+ *   Halting: vote supersteps run until one changes no vertex's cluster or max_iterations of them have run
+ *     (0 is legal: every vertex keeps its own id; < 0: JG_ERR_ARG).  iterations_out (nullable) =
+ *     memory().getIteration() of the Fulgora run (FulgoraGraphComputer.java:210-230, whose incrIteration also runs
+ *     on the terminating pass) = vote supersteps executed + 1, + 1 more with distribute_vote (the counting
+ *     superstep).
+ *   Errors: JG_DIR_OUT needs JG_ADJ_IN at build time, JG_DIR_BOTH needs JG_ADJ_BOTH, else JG_ERR_UNSUPPORTED.
+ *     JG_DIR_IN is JG_ERR_UNSUPPORTED: its vote strength divides by an in-degree, and a graph built with
+ *     JG_ADJ_OUT alone (the adjacency it would pull over) holds none.  One shard only: graphs of several shards
+ *     (logical shards, rank mode) get JG_ERR_UNSUPPORTED.
+ *   Stats: supersteps = iterations; levels = vote supersteps executed; compute_ms = the whole device run (HIP
+ *     events); kernel_ms_total / kernel_launches = the vote kernels alone; edges_traversed = vote supersteps x
+ *     entries of the adjacency read; algorithmic_bytes = the byte model of jg_peer.hip.
+ * Holds nothing afterwards and disturbs no held census, kept traversal or PageRank session. */
+int jg_peer_pressure(jg_graph* g, int32_t direction /* JG_DIR_OUT | JG_DIR_BOTH: the vote scope's edges */,
+                     int32_t distribute_vote, int32_t max_iterations,
+                     int64_t* cluster_vid_out /* [n], caller order, nullable */, int32_t* iterations_out /* nullable */);
 
 /* Combiner vertex programs (the DegreeCounter family, janusgraph-test/.../olap/OLAPTest.java:424-503):
  * x_0 = init[v] (NULL: every vertex sends 1), then `steps` supersteps of

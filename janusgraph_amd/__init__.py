@@ -13,7 +13,7 @@ from .graph import InMemoryGraph, load_graph_of_the_gods  # noqa: F401
 from .idmanager import IDManager, VertexIDType  # noqa: F401
 from .programs import (ClusterCountMapReduce, ClusterPopulationMapReduce, CombinerVertexProgram,  # noqa: F401
                        ConnectedComponentVertexProgram, DegreeCounter, DegreeMapper, PageRankMapReduce, PageRankTopMapReduce, PageRankVertexProgram, ShortestDistanceMapReduce,
-                       ShortestDistanceVertexProgram, ShortestPathVertexProgram)
+                       PeerPressureVertexProgram, ShortestDistanceVertexProgram, ShortestPathVertexProgram)
 
 __all__ = [
     "Context", "Graph", "JanusGpuError", "load", "ADJ_IN", "ADJ_OUT", "ADJ_BOTH", "DIR_IN", "DIR_OUT", "DIR_BOTH",
@@ -22,5 +22,5 @@ __all__ = [
     "IDManager", "VertexIDType", "PageRankVertexProgram", "PageRankMapReduce", "PageRankTopMapReduce", "ShortestDistanceVertexProgram",
     "ShortestDistanceMapReduce", "ConnectedComponentVertexProgram", "ShortestPathVertexProgram",
     "CombinerVertexProgram", "DegreeCounter", "DegreeMapper", "ClusterCountMapReduce",
-    "ClusterPopulationMapReduce", "COMBINE_SUM", "COMBINE_MIN", "COMBINE_MAX",
+    "ClusterPopulationMapReduce", "PeerPressureVertexProgram", "COMBINE_SUM", "COMBINE_MIN", "COMBINE_MAX",
 ]

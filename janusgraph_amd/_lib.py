@@ -47,6 +47,7 @@ EXPORTS = [
     "jg_bfs_kept_dag", "jg_bfs_kept_dag_read",
     "jg_cc_census", "jg_cc_census_read", "jg_cc_census_release",
     "jg_pagerank_top", "jg_pagerank_top_read", "jg_pagerank_top_release",
+    "jg_peer_pressure",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -207,6 +208,7 @@ def load():
         "jg_pagerank_top": ([_P, _i64, _P, _P], ctypes.c_int),
         "jg_pagerank_top_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
         "jg_pagerank_top_release": ([_P], ctypes.c_int),
+        "jg_peer_pressure": ([_P, _i32, _i32, _i32, _P, _P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -691,6 +693,17 @@ class Graph:
         it = ctypes.c_int32(0)
         check(load().jg_connected_components(self._h, _ptr(comp), ctypes.byref(it)))
         return comp, int(it.value)
+
+    def peer_pressure(self, direction=DIR_OUT, distribute_vote=False, max_iterations=30, want_clusters=True):
+        """jg_peer_pressure: PeerPressureVertexProgram over the edges `direction` (DIR_OUT: outE, votes pulled
+        over the IN adjacency; DIR_BOTH: bothE).  Returns (cluster_vid, iterations): each vertex's cluster id
+        (the vertex ids' order; ties go to the smallest id) and memory.getIteration().  want_clusters=False
+        passes a NULL output and returns None for the clusters."""
+        out = self._out(self.n, np.int64) if want_clusters else None
+        it = ctypes.c_int32(0)
+        check(load().jg_peer_pressure(self._h, int(direction), 1 if distribute_vote else 0, int(max_iterations),
+                                      _ptr(out), ctypes.byref(it)))
+        return out, int(it.value)
 
     CENSUS_READ_COMPONENTS = 1 << 22  # components per jg_cc_census_read call (64 MiB of pairs)
 

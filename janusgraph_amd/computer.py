@@ -25,7 +25,7 @@ from .computer_types import (Persist, ProgramNotSupported, ResultGraph, ResultMo
 from .graph import InMemoryGraph
 from .programs import (ClusterCountMapReduce, ClusterPopulationMapReduce, CombinerVertexProgram,
                        ConnectedComponentVertexProgram, PageRankTopMapReduce, PageRankVertexProgram,
-                       ShortestDistanceVertexProgram, ShortestPathVertexProgram)
+                       PeerPressureVertexProgram, ShortestDistanceVertexProgram, ShortestPathVertexProgram)
 
 
 class Memory:
@@ -161,7 +161,7 @@ class GpuGraphComputer:
         if vp is not None:
             if not isinstance(vp, (PageRankVertexProgram, ShortestDistanceVertexProgram,
                                    ConnectedComponentVertexProgram, ShortestPathVertexProgram,
-                                   CombinerVertexProgram)):
+                                   CombinerVertexProgram, PeerPressureVertexProgram)):
                 raise ProgramNotSupported(f"{type(vp).__name__} is not run by GpuGraphComputer; "
                                           f"delegate to FulgoraGraphComputer")
             self.map_reduces.extend(vp.get_map_reducers())
@@ -249,6 +249,20 @@ class GpuGraphComputer:
             finally:
                 g.close()
             props = {int(v): {vp.property: str(int(c))} for v, c in zip(vid, comp)}
+            return vid, props, it, {}
+        if isinstance(vp, PeerPressureVertexProgram):
+            vid, src, dst, _ = g0.snapshot()
+            direction = PeerPressureVertexProgram.SCOPES[vp.edges]
+            g = ctx.build(vid, src, dst, flags=_lib.ADJ_IN if direction == _lib.DIR_OUT else _lib.ADJ_BOTH)
+            try:
+                if g.info()["num_shards"] != 1:
+                    # jg_peer_pressure runs on one shard: the Java side keeps delegating
+                    raise ProgramNotSupported("PeerPressureVertexProgram is not run on a sharded graph; "
+                                              "delegate to FulgoraGraphComputer")
+                cluster, it = g.peer_pressure(direction, vp.distribute_vote, vp.max_iterations)
+            finally:
+                g.close()
+            props = {int(v): {vp.property: int(c)} for v, c in zip(vid, cluster)}  # the Long id, not a String
             return vid, props, it, {}
         if isinstance(vp, ShortestPathVertexProgram):
             return self._shortest_paths(ctx, vp)

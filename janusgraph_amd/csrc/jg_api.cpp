@@ -1631,4 +1631,12 @@ int jg_cc_census_release(jg_graph* g) {
     JG_GUARD_END
 }
 
+int jg_peer_pressure(jg_graph* g, int32_t direction, int32_t distribute_vote, int32_t max_iterations,
+                     int64_t* cluster_vid_out, int32_t* iterations_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::peer_pressure_run(g->impl, direction, distribute_vote, max_iterations, cluster_vid_out, iterations_out);
+    JG_GUARD_END
+}
+
 }  // extern "C"

@@ -639,6 +639,9 @@ NarrowRun narrow_bfs(Ctx& ctx, Shard& sh, const Csr& push, const Csr& pull, cons
                      int32_t* planes);
 void combine_run(Graph& g, int direction, int combiner, int wrap32, const int64_t* init, int steps, int64_t* out,
                  uint8_t* received_out);
+// jg_peer_pressure (jg_peer.hip): PeerPressureVertexProgram on one shard; cluster_out (nullable): caller order
+void peer_pressure_run(Graph& g, int direction, int distribute, int max_iterations, int64_t* cluster_out,
+                       int32_t* iterations_out);
 
 // Logical OR of a flag over all ranks (identity in single-process contexts).
 int allreduce_or(Graph& g, int flag);

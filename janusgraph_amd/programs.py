@@ -339,6 +339,63 @@ class PageRankTopMapReduce(MapReduce):
 PEER_PRESSURE_CLUSTER = "gremlin.peerPressureVertexProgram.cluster"
 
 
+class PeerPressureVertexProgram(VertexProgram):
+    """TinkerPop 3.4.6 PeerPressureVertexProgram (third party, not in the container; [TP-recall]): every
+    vertex starts in its own cluster and joins, superstep after superstep, the cluster with the largest summed
+    vote strength among its own vote and the votes it receives; with distributeVote a vertex's strength is
+    1 / (edges it votes along).  Votes travel along `edges` ("outE", the default, or "bothE").  The stored
+    cluster is the Long id of a vertex.  Among exactly tied clusters GpuGraphComputer takes the numerically
+    smallest id (TinkerPop's choice follows HashMap order and is not defined)."""
+
+    CLUSTER = PEER_PRESSURE_CLUSTER
+    VOTE_STRENGTH = "gremlin.peerPressureVertexProgram.voteStrength"
+    PROPERTY = "gremlin.peerPressureVertexProgram.property"
+    MAX_ITERATIONS = "gremlin.peerPressureVertexProgram.maxIterations"
+    DISTRIBUTE_VOTE = "gremlin.peerPressureVertexProgram.distributeVote"
+    EDGES = "gremlin.peerPressureVertexProgram.edgeTraversal"
+    SCOPES = {"outE": 1, "bothE": 3}  # -> jg_peer_pressure's direction (DIR_OUT / DIR_BOTH)
+    preferred_result_graph = ResultGraph.NEW
+    preferred_persist = Persist.VERTEX_PROPERTIES
+    compute_keys = (CLUSTER, VOTE_STRENGTH)
+
+    def load_state(self, conf):
+        self.property = conf.get(self.PROPERTY, self.CLUSTER)
+        self.max_iterations = int(conf.get(self.MAX_ITERATIONS, 30))
+        self.distribute_vote = bool(conf.get(self.DISTRIBUTE_VOTE, False))
+        self.edges = conf.get(self.EDGES, "outE")
+        if self.max_iterations < 0:
+            raise ValueError("maxIterations must not be negative")
+        if self.edges not in self.SCOPES:
+            raise ValueError(f"GpuGraphComputer runs PeerPressureVertexProgram over outE or bothE, not {self.edges!r}")
+        self.compute_keys = (self.property, self.VOTE_STRENGTH)
+
+    class Builder(_Builder):
+        def __init__(self):
+            super().__init__(PeerPressureVertexProgram)
+
+        def property(self, key):
+            self.configuration[PeerPressureVertexProgram.PROPERTY] = key
+            return self
+
+        def maxIterations(self, k):  # noqa: N802
+            self.configuration[PeerPressureVertexProgram.MAX_ITERATIONS] = int(k)
+            return self
+
+        def distributeVote(self, on):  # noqa: N802
+            self.configuration[PeerPressureVertexProgram.DISTRIBUTE_VOTE] = bool(on)
+            return self
+
+        def edges(self, scope):
+            if scope not in PeerPressureVertexProgram.SCOPES:
+                raise ValueError(f"edges must be 'outE' or 'bothE', not {scope!r}")
+            self.configuration[PeerPressureVertexProgram.EDGES] = scope
+            return self
+
+    @classmethod
+    def build(cls):
+        return cls.Builder()
+
+
 class _ClusterMrBuilder(_MrBuilder):
     def __init__(self, cls):
         super().__init__(cls)
@@ -408,4 +465,4 @@ class ClusterPopulationMapReduce(MapReduce):
 
 
 RECOGNISED = (PageRankVertexProgram, ShortestDistanceVertexProgram, ConnectedComponentVertexProgram,
-              ShortestPathVertexProgram, CombinerVertexProgram)
+              ShortestPathVertexProgram, CombinerVertexProgram, PeerPressureVertexProgram)

@@ -296,6 +296,17 @@ JNIEXPORT jint JNICALL FN(ccCensusRelease)(JNIEnv* env, jclass c, jlong g) {
     return jg_cc_census_release((jg_graph*)(intptr_t)g);
 }
 
+JNIEXPORT jint JNICALL FN(peerPressure)(JNIEnv* env, jclass c, jlong g, jint direction, jint distribute_vote,
+                                        jint max_iterations, jobject cluster_out, jintArray iterations_out) {
+    (void)c;
+    int32_t it = 0;
+    int st = jg_peer_pressure((jg_graph*)(intptr_t)g, direction, distribute_vote, max_iterations,
+                              (int64_t*)buf(env, cluster_out), &it);
+    jint v = it;
+    (*env)->SetIntArrayRegion(env, iterations_out, 0, 1, &v);
+    return st;
+}
+
 JNIEXPORT jint JNICALL FN(pagerankTop)(JNIEnv* env, jclass c, jlong g, jlong k, jlongArray listed_out,
                                        jdoubleArray select_ms_out) {
     (void)c;

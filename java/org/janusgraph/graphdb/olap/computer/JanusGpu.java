@@ -118,6 +118,11 @@ final class JanusGpu {
                                    ByteBuffer populationOut);
     /** jg_cc_census_release: drops the held census before the graph goes. */
     static native int ccCensusRelease(long graph);
+    /** jg_peer_pressure: PeerPressureVertexProgram on one shard over the edges direction (1 outE, 3 bothE);
+     *  clusterVidOut: an int64 direct buffer of n cluster ids (null: not wanted), iterationsOut[0] =
+     *  memory.getIteration().  Ties go to the numerically smallest cluster id. */
+    static native int peerPressure(long graph, int direction, int distributeVote, int maxIterations,
+                                   ByteBuffer clusterVidOut, int[] iterationsOut);
     /** jg_pagerank_top: the min(k, n) highest-ranked vertices of the held PageRank session, selected on the
      *  device (rank descending, ties by snapshot order); listedOut[0] = the records listed, selectMsOut[0] =
      *  the select's device time.  The list stays with the graph for pagerankTopRead. */
