@@ -559,6 +559,8 @@ int jg_graph_sync(jg_graph* g);
  *     "merge_hot" [-1, 2^30]; "merge_off32" [0, 1];
  *     "sd_delta" [-1, 2^30]; "sd_dist32" [0, 2]; "merge_pack" 0 | 1 | 24; "merge_stage<i>" -1 | 0 | 64 | 128 | 256 | 512;
  *     read at build: "band<i>_deg" (>= -1), "band<i>_bit" (0 or [3, 8]), "band<i>_sub" (power of two <= 256);
+ *     "edgestore_chunk_entries", "edgestore_chunk_bytes" (>= 1): the chunk limits of jg_graph_build_edgestore
+ *     (tests lower them; rows never split, so a larger row is a chunk of its own);
  *   retired (their variants were measured slower and removed; accepted and ignored): "pull_unroll",
  *     "pull_nt", "pull_lds", "light_lds", "slice_lds", "pull_short", "pull_overlap", "bfs_persistent".
  * Unknown key or value out of range: JG_ERR_ARG. */

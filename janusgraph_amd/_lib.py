@@ -237,7 +237,8 @@ def _ptr(a):
 def tune_set(key: str, value: int):
     """Process-wide performance knob (results are unaffected; the list is jg_api.cpp jg_tune_set), e.g.
     msbfs_exit, bfs_narrow, and at graph build time pull_split, band<i>_deg, band<i>_bit, halo (sharded
-    graphs: compact vectors + sparse halo exchange instead of the dense allgather)."""
+    graphs: compact vectors + sparse halo exchange instead of the dense allgather);
+    edgestore_chunk_entries / edgestore_chunk_bytes: the chunk limits of build_edgestore (tests)."""
     check(load().jg_tune_set(key.encode(), int(value)))
 
 

@@ -764,6 +764,9 @@ int jg_tune_set(const char* key, int64_t value) {
     } else if (k == "bfs_td_split_min" || k == "bfs_td_split_max") {
         JG_ARG(value >= 1 && value <= INT32_MAX, "bfs_td_split_min / _max must be in [1, 2^31)");
         (k == "bfs_td_split_min" ? t.bfs_td_split_min : t.bfs_td_split_max) = value;
+    } else if (k == "edgestore_chunk_entries" || k == "edgestore_chunk_bytes") {
+        JG_ARG(value >= 1, "edgestore_chunk_entries / _bytes must be at least 1");
+        (k == "edgestore_chunk_entries" ? t.edgestore_chunk_entries : t.edgestore_chunk_bytes) = value;
     } else if (k == "merge_pack") {
         JG_ARG(value == 0 || value == 1 || value == 24, "merge_pack must be 0 (32 bits), 1 (automatic) or 24 (at least 24)");
         t.merge_pack = (int)value;

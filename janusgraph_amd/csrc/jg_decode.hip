@@ -258,6 +258,7 @@ struct DecodeOut {
 // A block whose range exceeds the stage (entries with long property values) reads global memory.
 // The byte array is allocated with kBytePad slack, so the dword loads may run past its end.
 constexpr int kStageWords = 4096;  // 16 KB of LDS per block (a 1024-entry chunk of ~10-byte entries)
+                                   // (restated as STAGE_WORDS in tests/test_edgestore_paths_host.py)
 constexpr int64_t kBytePad = 64;
 
 struct Stage {
@@ -383,8 +384,8 @@ __device__ __forceinline__ int64_t row_of_entry(const int64_t* __restrict__ row_
 // for coalescing): one staged byte range, one staged window of row offsets and keep flags, so the
 // dependent global round trips (row lookup, keep, varint bytes) are paid once per chunk.
 constexpr int kEpt = 4;
-constexpr int64_t kChunk = (int64_t)kEpt * kBlock;
-constexpr int kRowWin = 1024;
+constexpr int64_t kChunk = (int64_t)kEpt * kBlock;  // CHUNK in tests/test_edgestore_paths_host.py
+constexpr int kRowWin = 1024;                       // ROW_WIN in tests/test_edgestore_paths_host.py
 
 // block_row[k] = the row holding entry k * kChunk (one thread per row writes the boundaries inside it)
 __global__ void block_rows_kernel(const int64_t* __restrict__ row_off, int64_t nrows, int64_t* __restrict__ block_row) {
@@ -905,7 +906,7 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
                     bad[t] = e;
                     return;
                 }
-                if (len >= 256) w = true;
+                if (len >= 256) w = true;  // WIDE_LEN in tests/test_edgestore_paths_host.py
                 len8[e] = (uint8_t)len;
                 vp8[e] = (uint8_t)vp;
             }
@@ -1127,7 +1128,8 @@ void EdgestoreDecoder::finish() {
 
 void add_in_chunks(EdgestoreDecoder& dec, const EdgestoreRows& r) {
     check_rows(r);
-    constexpr int64_t kChunkEntries = (int64_t)4 << 20, kChunkBytes = (int64_t)64 << 20;
+    // jg_tune_set edgestore_chunk_entries / _bytes (defaults 4 Mi entries, 64 MB)
+    const int64_t chunk_entries = tune().edgestore_chunk_entries, chunk_bytes = tune().edgestore_chunk_bytes;
     // chunk boundaries are cut at entry offsets: the first and last must lie inside the bytes (each
     // chunk then checks its own entries)
     if (r.nentries > 0 && (r.entry_off[0] < 0 || r.entry_off[r.nentries] > r.nbytes))
@@ -1137,8 +1139,8 @@ void add_in_chunks(EdgestoreDecoder& dec, const EdgestoreRows& r) {
     while (lo < r.nrows || (lo == 0 && r.nrows == 0)) {
         int64_t hi = lo + 1;
         const int64_t e0 = r.nrows ? r.row_off[lo] : 0;
-        while (hi < r.nrows && r.row_off[hi + 1] - e0 <= kChunkEntries &&
-               (!has_entries || r.entry_off[r.row_off[hi + 1]] - r.entry_off[e0] <= kChunkBytes))
+        while (hi < r.nrows && r.row_off[hi + 1] - e0 <= chunk_entries &&
+               (!has_entries || r.entry_off[r.row_off[hi + 1]] - r.entry_off[e0] <= chunk_bytes))
             ++hi;
         if (r.nrows == 0) hi = 0;
         EdgestoreRows c = r;

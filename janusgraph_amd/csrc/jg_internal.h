@@ -742,6 +742,10 @@ struct Tune {
                                       // base when the vector is at most 4 GiB (0: 64-bit addresses always; tests)
     int merge_pack = 1;               // build time: band entries packed in 20/24 bits when the vector allows
                                       // (0: 32 bits, 24: at least 24; tests)
+    // the one-shot edgestore build (add_in_chunks, jg_decode.hip): a chunk of whole rows holds at most this
+    // many entries and bytes (a larger row is a chunk of its own); tests lower them to reach the rebasing
+    int64_t edgestore_chunk_entries = (int64_t)4 << 20;
+    int64_t edgestore_chunk_bytes = (int64_t)64 << 20;
 };
 Tune& tune();
 // rank mode over jg_transport callbacks (jg_api.cpp)
