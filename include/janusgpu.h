@@ -41,6 +41,9 @@
  *   jg_peer_pressure
  *       TinkerPop PeerPressureVertexProgram (weighted mode of the neighbours' cluster votes over outE or
  *       bothE, optional vote distribution), under the same loop; ties go to the smallest cluster id
+ *   jg_sssp_keep / jg_sssp_kept_dag
+ *       TinkerPop ShortestPathVertexProgram with distanceProperty(key) and edgeDirection(dir) [TP-recall]:
+ *       summed edge weights along the direction's edges, and the minimum-weight paths' predecessor DAG
  *   jg_combine_steps
  *       the same loop for sum/min/max MessageCombiner programs (OLAPTest.DegreeCounter,
  *       janusgraph-test/.../olap/OLAPTest.java:424-503; VertexState.java:85-114)
@@ -71,7 +74,8 @@ extern "C" {
  * Still 3 (entry points only, no layout change): jg_builder_keep_labels, jg_builder_add_labeled_edges,
  * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added; jg_cc_census, jg_cc_census_read,
  * jg_cc_census_release added; jg_pagerank_top, jg_pagerank_top_read, jg_pagerank_top_release added;
- * jg_peer_pressure added. */
+ * jg_peer_pressure added; JG_ADJ_WEIGHT_BOTH, jg_sssp_keep, jg_sssp_kept_row, jg_sssp_kept_release,
+ * jg_sssp_kept_dag, jg_sssp_kept_dag_read added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -87,6 +91,10 @@ extern "C" {
 #define JG_ADJ_OUT  1u  /* out-adjacency: rows = source vertex (bottom-up of IN traversals)        */
 #define JG_ADJ_IN   2u  /* in-adjacency:  rows = target vertex (PageRank pull, SD push)           */
 #define JG_ADJ_BOTH 4u  /* symmetrised:   rows = every vertex, a self-loop appears twice (BOTH)   */
+/* With JG_ADJ_BOTH and edge weights only (a weight array, or a builder whose chunks carry weights; anything
+ * else is JG_ERR_ARG): the BOTH adjacency carries each edge's weight on both of its entries (jg_sssp_keep
+ * with JG_DIR_BOTH relaxes it).  Without the flag a build is what it was before the flag existed. */
+#define JG_ADJ_WEIGHT_BOTH 8u
 
 /* ---- traversal direction (the MessageScope.Local incident traversal) ---- */
 #define JG_DIR_OUT  1   /* follow u->v edges from u          */
@@ -429,6 +437,54 @@ int jg_bfs_kept_dag(jg_graph* g, int32_t s, const uint8_t* target, int64_t* num_
  * JG_ERR_ARG. */
 int jg_bfs_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
                          int64_t* off_out, int32_t* pred_out);
+
+/* Weighted single-source shortest distances whose distance plane stays on the device (ShortestPathVertexProgram
+ * with a distanceProperty): dist[v] = the smallest summed weight of a path source -> v whose edges are followed
+ * in `direction`: JG_DIR_OUT along u->v (relaxes the OUT adjacency), JG_DIR_IN against u->v (the IN adjacency:
+ * what jg_shortest_distance computes from its seed with an unbounding max_depth), JG_DIR_BOTH either way (the
+ * BOTH adjacency built with JG_ADJ_WEIGHT_BOTH).  The engine is jg_shortest_distance's near-far delta-stepping.
+ *   Preconditions: every weight of the relaxed adjacency is >= 1 (a weight <= 0 anywhere in it: JG_ERR_ARG;
+ *     zero-weight edges would make the tight-edge graph of jg_sssp_kept_dag cyclic); a JG_WEIGHT_ABSENT entry
+ *     that a relaxation crosses: JG_ERR_ARG, as in jg_shortest_distance.  A graph without weights, or without
+ *     the relaxed adjacency (JG_DIR_BOTH: without JG_ADJ_WEIGHT_BOTH): JG_ERR_UNSUPPORTED.  A bad direction:
+ *     JG_ERR_ARG.  An unknown source_vid: every distance absent, JG_OK.
+ *   The plane stays with the graph until the next jg_sssp_keep, jg_sssp_kept_release or jg_graph_destroy; it is
+ *     independent of jg_bfs_keep's rows and DAG (neither family drops the other's holdings).  A failed
+ *     jg_sssp_keep holds nothing.
+ *   jg_sssp_kept_row copies it out: dist_out[n] int64 in caller order, JG_DIST_ABSENT = unreached; nothing
+ *     kept: JG_ERR_STATE.  jg_sssp_kept_release drops the plane and its DAG (JG_OK when none is held).
+ *   One shard only: graphs of several shards (logical shards, rank mode) get JG_ERR_UNSUPPORTED.
+ *   Stats: compute_ms = up to the distances being final on the device (HIP events), levels = near passes. */
+int jg_sssp_keep(jg_graph* g, int64_t source_vid, int32_t direction);
+int jg_sssp_kept_row(jg_graph* g, int64_t* dist_out);
+int jg_sssp_kept_release(jg_graph* g);
+
+/* The minimum-weight-path predecessor DAG of the kept distance plane (jg_sssp_keep), built on the device: as
+ * jg_bfs_kept_dag with distance in place of depth.  target[n] (caller order, nullable = every such vertex).
+ *   Targets: vertices with a present distance, <= max_distance when max_distance >= 0, and target[] set.
+ *   Vertices: the targets and every vertex on a minimum-weight path from the source to one of them.  If any
+ *     target is reached the source is listed last, with an empty predecessor range.  No target reached: 0
+ *     vertices, 0 entries, farthest -1, JG_OK.
+ *   Order: non-increasing distance; inside one distance unspecified, but the same on every call with the same
+ *     arguments.
+ *   Predecessors of v: its distinct neighbours u in the reverse adjacency with dist[u] present and
+ *     dist[u] + w(u,v) == dist[v] (a tight edge), each once, in the order jg_graph_neighbors returns them for
+ *     the reverse direction, first qualifying occurrence kept.  Of parallel edges only the lightest can be
+ *     tight; with weights >= 1 a self-loop never is.  The adjacency read is the reverse of the kept
+ *     direction's: JG_DIR_BOTH reads BOTH, JG_DIR_OUT reads IN, JG_DIR_IN reads OUT; JG_ERR_UNSUPPORTED if it
+ *     was not built (with weights).
+ *   farthest_out: the largest distance of a target.  All three outputs are nullable.
+ * The DAG has its own buffers (a jg_bfs_kept_dag DAG may be held at the same time) and stays with the graph
+ * until the next jg_sssp_kept_dag, jg_sssp_keep, jg_sssp_kept_release or jg_graph_destroy.  No plane kept:
+ * JG_ERR_STATE.  Stats: compute_ms = the DAG build (the target mask's copy in and the read-back are outside),
+ * levels = the backward sweep's rounds that had rows, edges_traversed = the summed row lengths of the DAG
+ * vertices but the source, kernel_launches = launches of the walk kernels. */
+int jg_sssp_kept_dag(jg_graph* g, const uint8_t* target, int64_t max_distance /* < 0: none */,
+                     int64_t* num_vertices_out, int64_t* num_entries_out, int64_t* farthest_out);
+/* DAG vertices [first, first + count), as jg_bfs_kept_dag_read with dist_out[count] int64 distances.  No DAG
+ * held: JG_ERR_STATE; a range outside [0, num_vertices]: JG_ERR_ARG. */
+int jg_sssp_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
+                          int64_t* off_out, int32_t* pred_out);
 
 /* Adjacency of vertices rows[0, nrows) (output-order indices), in output-order indices: the host copy
  * of the snapshot a path walk-back reads where Fulgora re-reads each vertex's preloaded BOTH slice

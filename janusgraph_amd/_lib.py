@@ -24,6 +24,7 @@ JG_ERR_UNSUPPORTED = -5
 JG_ERR_STATE = -6
 
 ADJ_OUT, ADJ_IN, ADJ_BOTH = 1, 2, 4
+ADJ_WEIGHT_BOTH = 8  # with ADJ_BOTH and weights: the BOTH rows carry each edge's weight (sssp_keep over DIR_BOTH)
 DIR_OUT, DIR_IN, DIR_BOTH = 1, 2, 3
 COMBINE_SUM, COMBINE_MIN, COMBINE_MAX = 0, 1, 2
 FULGORA_HARD_QUERY_LIMIT = 100000
@@ -48,6 +49,7 @@ EXPORTS = [
     "jg_cc_census", "jg_cc_census_read", "jg_cc_census_release",
     "jg_pagerank_top", "jg_pagerank_top_read", "jg_pagerank_top_release",
     "jg_peer_pressure",
+    "jg_sssp_keep", "jg_sssp_kept_row", "jg_sssp_kept_release", "jg_sssp_kept_dag", "jg_sssp_kept_dag_read",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -209,6 +211,11 @@ def load():
         "jg_pagerank_top_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
         "jg_pagerank_top_release": ([_P], ctypes.c_int),
         "jg_peer_pressure": ([_P, _i32, _i32, _i32, _P, _P], ctypes.c_int),
+        "jg_sssp_keep": ([_P, _i64, _i32], ctypes.c_int),
+        "jg_sssp_kept_row": ([_P, _P], ctypes.c_int),
+        "jg_sssp_kept_release": ([_P], ctypes.c_int),
+        "jg_sssp_kept_dag": ([_P, _P, _i64, _P, _P, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -660,6 +667,71 @@ class Graph:
             check(load().jg_bfs_kept_dag_read(self._h, first, last - first, None, None, None, into))
             first = last
         return vertex, depth, off, pred
+
+    def sssp_keep(self, source, direction=DIR_BOTH):
+        """jg_sssp_keep: the smallest summed weights from `source` along `direction` (weights >= 1; DIR_BOTH
+        needs ADJ_BOTH | ADJ_WEIGHT_BOTH), kept on the device for sssp_kept_row and sssp_kept_dag."""
+        check(load().jg_sssp_keep(self._h, int(source), int(direction)))
+
+    def sssp_kept_row(self, out=None):
+        """jg_sssp_kept_row: the kept distances, into `out` (n int64) or a new array; DIST_ABSENT = unreached."""
+        if out is not None and not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.ndim == 1
+                                    and out.flags.c_contiguous and out.size >= self.n):
+            raise ValueError("out must be a C-contiguous int64 array of at least n elements")
+        row = self._out(self.n, np.int64) if out is None else out
+        check(load().jg_sssp_kept_row(self._h, _ptr(row)))
+        return row
+
+    def sssp_kept_release(self):
+        check(load().jg_sssp_kept_release(self._h))
+
+    def sssp_kept_dag_build(self, target=None, max_distance=-1):
+        """jg_sssp_kept_dag: builds the tight-edge predecessor DAG of the kept distances on the device (target:
+        one flag per vertex, None = every reached vertex; max_distance < 0: no bound).  Returns
+        (num_vertices, num_entries, farthest)."""
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, np.uint8)
+            if t.ndim != 1 or len(t) != self.n:
+                raise ValueError("target needs one flag per vertex")
+        nv, ne, far = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(load().jg_sssp_kept_dag(self._h, _ptr(t), int(max_distance), ctypes.byref(nv), ctypes.byref(ne),
+                                      ctypes.byref(far)))
+        return nv.value, ne.value, far.value
+
+    def sssp_kept_dag_read(self, first, count, want_pred=True):
+        """jg_sssp_kept_dag_read of the held DAG's vertices [first, first + count): (vertex, dist, off, pred)
+        with ABSOLUTE offsets; pred = entries [off[0], off[-1]) (None unless want_pred)."""
+        vertex = np.empty(max(count, 1), np.int32)
+        dist = np.empty(max(count, 1), np.int64)
+        off = np.empty(count + 1, np.int64)
+        check(load().jg_sssp_kept_dag_read(self._h, int(first), int(count), _ptr(vertex), _ptr(dist), _ptr(off), None))
+        pred = None
+        if want_pred:
+            k = int(off[-1] - off[0])
+            pred = np.empty(max(k, 1), np.int32)
+            check(load().jg_sssp_kept_dag_read(self._h, int(first), int(count), None, None, None, _ptr(pred)))
+            pred = pred[:k]
+        return vertex[:count], dist[:count], off, pred
+
+    def sssp_kept_dag(self, target=None, max_distance=-1):
+        """The minimum-weight-path predecessor DAG of the kept distances (sssp_keep): (vertex, dist, off, pred).
+        vertex[j] (output-order index, non-increasing dist[j], the source last) has the distinct tight
+        predecessors pred[off[j]:off[j + 1]] in jg_graph_neighbors order of the reverse direction.  Built on
+        the device (jg_sssp_kept_dag), read in vertex ranges as bfs_kept_dag."""
+        nv, ne, _ = self.sssp_kept_dag_build(target, max_distance)
+        if ne <= self.DAG_READ_ENTRIES:
+            return self.sssp_kept_dag_read(0, nv)
+        vertex, dist, off, _ = self.sssp_kept_dag_read(0, nv, want_pred=False)
+        pred = np.empty(ne, np.int32)
+        first = 0
+        while first < nv:
+            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
+            last = min(max(last, first + 1), nv)
+            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * int(off[first]))
+            check(load().jg_sssp_kept_dag_read(self._h, first, last - first, None, None, None, into))
+            first = last
+        return vertex, dist, off, pred
 
     def neighbors(self, rows, direction=DIR_BOTH):
         """jg_graph_neighbors: (off, nbr) CSR of the given output-order rows, in output-order indices."""

@@ -321,7 +321,15 @@ class GpuGraphComputer:
         device (jg_bfs_keep) and each source's predecessor DAG is built there (jg_bfs_kept_dag): only the DAG
         comes back, and DevicePathDag enumerates it.  Sharded graphs take one depth row per source
         (jg_bfs_rows) and PathDag walks back over the snapshot's BOTH adjacency on the host.  Both routes
-        give the same paths in the same order."""
+        give the same paths in the same order.
+
+        edgeDirection("out" | "in") follows the edges one way: the same two routes with that direction, the
+        predecessors read from the reverse adjacency (ADJ_IN | ADJ_OUT is built instead of ADJ_BOTH).
+        distanceProperty(key) goes to _weighted_shortest_paths."""
+        if vp.distance_property is not None:
+            return self._weighted_shortest_paths(ctx, vp)
+        direction = _PATH_DIRECTIONS[vp.edge_direction]
+        reverse = _REVERSE_DIRECTION[direction]
         vid, src, dst, _ = self.graph.snapshot()
         index = {int(v): i for i, v in enumerate(vid.tolist())}
         sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
@@ -329,19 +337,21 @@ class GpuGraphComputer:
         if vp.targets is not None:
             target = np.zeros(len(vid), bool)
             target[[index[t] for t in vp.targets if t in index]] = True
-        g = ctx.build(vid, src, dst, flags=_lib.ADJ_BOTH)
+        both = direction == _lib.DIR_BOTH
+        g = ctx.build(vid, src, dst, flags=_lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT)
         paths, max_level = [], 0
         max_depth = -1 if vp.max_distance is None else vp.max_distance
         try:
             on_device = g.info()["num_shards"] == 1
-            dag = DevicePathDag(len(vid)) if on_device else PathDag(g.neighbors, len(vid))
+            neighbors = g.neighbors if both else (lambda rows: g.neighbors(rows, reverse))
+            dag = DevicePathDag(len(vid)) if on_device else PathDag(neighbors, len(vid))
             for b0 in range(0, len(sources), SOURCES_PER_BFS):
                 batch = sources[b0:b0 + SOURCES_PER_BFS]
                 if on_device:
-                    g.bfs_keep(vid[batch], _lib.DIR_BOTH, max_depth)
+                    g.bfs_keep(vid[batch], direction, max_depth)
                     results = (dag.paths(g.bfs_kept_dag(j, target), s, target) for j, s in enumerate(batch))
                 else:
-                    rows = g.bfs_rows(vid[batch], _lib.DIR_BOTH, max_depth)
+                    rows = g.bfs_rows(vid[batch], direction, max_depth)
                     results = (dag.paths(depth, s, target) for s, depth in zip(batch, rows))
                 for got, deepest in results:
                     max_level = max(max_level, deepest)
@@ -349,6 +359,48 @@ class GpuGraphComputer:
         finally:
             g.close()
         return vid, {}, max_level + 1, {vp.SHORTEST_PATHS: paths}
+
+    def _weighted_shortest_paths(self, ctx, vp):
+        """ShortestPathVertexProgram with a distanceProperty: per source, the smallest summed weights stay on
+        the device (jg_sssp_keep, delta-stepping along edgeDirection), the tight-edge predecessor DAG to the
+        targets within maxDistance (inclusive, on the summed weight) is built there (jg_sssp_kept_dag), and
+        DevicePathDag enumerates it: sources in the given order, targets ascending, first predecessor first.
+        Refused (the caller delegates): an edge without the property or with a weight < 1 (zero-weight edges
+        make the tight-edge graph cyclic; TinkerPop reads any Number), and graphs of several shards.
+        The iteration count is 1 + the edges of the longest returned path (1 when there is none): what
+        max_level + 1 means on the hop route; this project's rule, not pinned by any reference test."""
+        direction = _PATH_DIRECTIONS[vp.edge_direction]
+        vid, src, dst, w = self.graph.snapshot(weight_property=vp.distance_property)
+        if len(w) and int(w.min()) < 1:
+            missing = int((w == _lib.WEIGHT_ABSENT).sum())
+            raise ProgramNotSupported(
+                f"ShortestPathVertexProgram with distanceProperty {vp.distance_property!r} is not run by "
+                f"GpuGraphComputer: " + (f"{missing} edge(s) lack the property" if missing else
+                                         "an edge has a weight < 1") + "; delegate to FulgoraGraphComputer")
+        index = {int(v): i for i, v in enumerate(vid.tolist())}
+        sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
+        target = None
+        if vp.targets is not None:
+            target = np.zeros(len(vid), bool)
+            target[[index[t] for t in vp.targets if t in index]] = True
+        both = direction == _lib.DIR_BOTH
+        g = ctx.build(vid, src, dst, w, flags=(_lib.ADJ_BOTH | _lib.ADJ_WEIGHT_BOTH) if both
+                      else _lib.ADJ_IN | _lib.ADJ_OUT)
+        paths, longest = [], 0
+        max_distance = -1 if vp.max_distance is None else vp.max_distance
+        try:
+            if g.info()["num_shards"] != 1:
+                raise ProgramNotSupported("ShortestPathVertexProgram with a distanceProperty is not run on a sharded "
+                                          "graph; delegate to FulgoraGraphComputer")
+            dag = DevicePathDag(len(vid))
+            for s in sources:
+                g.sssp_keep(vid[s], direction)
+                got, _ = dag.paths(g.sssp_kept_dag(target, max_distance), s, target)
+                longest = max([longest] + [len(p) - 1 for p in got])
+                paths.extend([int(vid[x]) for x in p] for p in got)
+        finally:
+            g.close()
+        return vid, {}, longest + 1, {vp.SHORTEST_PATHS: paths}
 
     def _write_back(self, props):
         if self.persist_mode is Persist.NOTHING:
@@ -363,6 +415,8 @@ class GpuGraphComputer:
 
 
 SOURCES_PER_BFS = 64  # jg_bfs_rows: one bit-parallel pass per 64 sources
+_PATH_DIRECTIONS = {"out": _lib.DIR_OUT, "in": _lib.DIR_IN, "both": _lib.DIR_BOTH}  # edgeDirection
+_REVERSE_DIRECTION = {_lib.DIR_OUT: _lib.DIR_IN, _lib.DIR_IN: _lib.DIR_OUT, _lib.DIR_BOTH: _lib.DIR_BOTH}
 
 
 class PathDag:
@@ -429,7 +483,9 @@ class PathDag:
 class DevicePathDag:
     """PathDag.paths' result from a predecessor DAG built on the device (Graph.bfs_kept_dag):
     dag = (vertex, depth, off, pred), vertex[j] with the predecessors pred[off[j]:off[j + 1]], depth
-    non-increasing.  Paths are enumerated as PathDag does: targets ascending, first predecessor first."""
+    non-increasing.  Paths are enumerated as PathDag does: targets ascending, first predecessor first.
+    The weighted DAG (Graph.sssp_kept_dag) has distances in the depth's place: the enumeration reads only
+    the first of them, for the second value it returns (the largest depth / distance of a target)."""
 
     def __init__(self, n):
         self.n = n

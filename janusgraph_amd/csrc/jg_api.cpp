@@ -918,6 +918,12 @@ int jg_ctx_set_profiling(jg_ctx* ctx, int enable) {
     JG_GUARD_END
 }
 
+// JG_ADJ_WEIGHT_BOTH goes with JG_ADJ_BOTH and edge weights only
+static bool weight_both_ok(uint32_t flags, bool has_weights) {
+    return !(flags & JG_ADJ_WEIGHT_BOTH) || ((flags & JG_ADJ_BOTH) && has_weights);
+}
+static const char* const kWeightBothRule = "JG_ADJ_WEIGHT_BOTH needs JG_ADJ_BOTH and edge weights";
+
 int jg_graph_build(jg_ctx* ctx, const int64_t* vid, int64_t n, const int64_t* src, const int64_t* dst,
                    const int32_t* weight, int64_t m, uint32_t flags, jg_graph** out) {
     JG_GUARD_BEGIN
@@ -927,7 +933,8 @@ int jg_graph_build(jg_ctx* ctx, const int64_t* vid, int64_t n, const int64_t* sr
     JG_ARG(m == 0 || (src && dst), "src/dst is null");
     JG_ARG(n < (int64_t)INT32_MAX, "more than 2^31-1 vertices");
     JG_ARG(m < (int64_t)UINT32_MAX, "more than 2^32-1 edges");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~7u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG(weight_both_ok(flags, weight != nullptr), kWeightBothRule);
     *out = nullptr;
     jg::Ctx& c = ctx->impl;
     auto gh = std::make_unique<jg_graph>(&c);
@@ -966,7 +973,8 @@ int jg_graph_build_edgestore(jg_ctx* ctx, const uint64_t* row_keys, int64_t nrow
                              jg_graph** out) {
     JG_GUARD_BEGIN
     JG_ARG(ctx && out, "null argument");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~7u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG(weight_both_ok(flags, false), kWeightBothRule);
     const jg::EdgestoreRows r{row_keys, nrows,     row_entry_off, bytes,    nbytes,        entry_off,
                               value_pos, nentries, type_ids,      type_mult, ntypes,       partition_bits};
     *out = nullptr;  // the decoder validates the rows and entries as it stages them
@@ -1172,7 +1180,8 @@ int jg_builder_add_rows(jg_builder* b, const uint64_t* row_keys, int64_t nrows, 
 int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
     JG_GUARD_BEGIN
     JG_ARG(b && out, "null argument");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~7u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG(weight_both_ok(flags, b->mode == 2 ? (b->dec && b->dec->weighted == 1) : b->weights == 1), kWeightBothRule);
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     *out = nullptr;
     jg::Ctx& c = *b->ctx;
@@ -1237,7 +1246,8 @@ int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
 int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabels, uint32_t flags, jg_graph** out) {
     JG_GUARD_BEGIN
     JG_ARG(b && out, "null argument");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~7u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG(weight_both_ok(flags, b->mode == 2 ? (b->dec && b->dec->weighted == 1) : b->weights == 1), kWeightBothRule);
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     if (!b->keep_labels) jg::fail(JG_ERR_STATE, "jg_builder_finish_labels needs jg_builder_keep_labels before the first chunk");
     static_assert(JG_MAX_SCOPE_LABELS == jg::kScopeMaxLabels, "the header's cap is the select's");
@@ -1315,7 +1325,8 @@ int jg_graph_build_rmat(jg_ctx* ctx, int scale, int edgefactor, uint64_t seed, u
     JG_GUARD_BEGIN
     JG_ARG(ctx && out, "null argument");
     JG_ARG(scale >= 1 && scale <= 30 && edgefactor >= 1 && edgefactor <= 64, "bad RMAT scale/edgefactor");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~7u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG(weight_both_ok(flags, false), kWeightBothRule);
     *out = nullptr;
     const int64_t n = 1ll << scale, m = (int64_t)edgefactor << scale;
     JG_ARG(m < (int64_t)UINT32_MAX, "too many edges");
@@ -1574,6 +1585,43 @@ int jg_bfs_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* ver
     JG_GUARD_BEGIN
     JG_ARG(g, "null graph");
     jg::bfs_kept_dag_read(g->impl, first, count, vertex_out, depth_out, off_out, pred_out);
+    JG_GUARD_END
+}
+
+int jg_sssp_keep(jg_graph* g, int64_t source_vid, int32_t direction) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_keep(g->impl, source_vid, direction);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_row(jg_graph* g, int64_t* dist_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g && dist_out, "null argument");
+    jg::sssp_kept_row(g->impl, dist_out);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_release(jg_graph* g) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_release(g->impl);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag(jg_graph* g, const uint8_t* target, int64_t max_distance, int64_t* num_vertices_out,
+                     int64_t* num_entries_out, int64_t* farthest_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag(g->impl, target, max_distance, num_vertices_out, num_entries_out, farthest_out);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
+                          int64_t* off_out, int32_t* pred_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag_read(g->impl, first, count, vertex_out, dist_out, off_out, pred_out);
     JG_GUARD_END
 }
 

@@ -1299,7 +1299,9 @@ void build_graph_from_dense(Graph& g, DenseEdges& e) {
                 build_csr(sh, a, w, sh.out, s);
             }
         }
-        if (g.flags & JG_ADJ_BOTH) build_pull_csr(2, all, nullptr, sh.both, sh.plan_both, sh.halo_both);
+        // (JG_ADJ_WEIGHT_BOTH: each edge's weight on both of its entries, for jg_sssp_keep over JG_DIR_BOTH)
+        if (g.flags & JG_ADJ_BOTH)
+            build_pull_csr(2, all, (g.flags & JG_ADJ_WEIGHT_BOTH) ? w : nullptr, sh.both, sh.plan_both, sh.halo_both);
         JG_HIP(hipStreamSynchronize(s));
         if (first) {  // the first shard's padded ids stay with the graph (vid -> shard / row lookups)
             g.padded_dev = std::move(padded);

@@ -267,6 +267,12 @@ struct Shard {
     // descending): caller-order vertex and depth, offsets into dag_pred, caller-order predecessors
     DevBuf<int32_t> dag_vertex, dag_depth, dag_pred;
     DevBuf<int64_t> dag_off;                 // [dag_nv + 1]
+    // jg_sssp_keep's distance plane ([rows] int64, local row order, LLONG_MIN: absent) and the tight-edge
+    // predecessor DAG of it (jg_sssp_kept_dag; Graph::wdag_nv vertices, distance descending): buffers of
+    // their own, so that a kept BFS row and its DAG can be held at the same time
+    DevBuf<long long> sssp_dist;
+    DevBuf<int32_t> wdag_vertex, wdag_pred;
+    DevBuf<int64_t> wdag_dist, wdag_off;     // [wdag_nv], [wdag_nv + 1]
     // the held component census (jg_cc_census, jg_census.hip; Graph::census_listed pairs, population
     // descending): the component's vertex id and its population.  Its own buffers, not program scratch.
     DevBuf<int64_t> census_vid, census_pop;
@@ -315,6 +321,9 @@ struct Graph {
     int kept_nsrc = 0;  // depth rows kept by jg_bfs_keep
     int kept_dir = 0;   // the direction of that traversal (jg_bfs_kept_dag reads the reverse adjacency)
     int64_t dag_nv = -1, dag_ne = 0;  // the held predecessor DAG (Shard::dag_*); -1: none
+    bool sssp_kept = false;           // jg_sssp_keep's plane is held (Shard::sssp_dist)
+    int sssp_dir = 0;                 // its direction (jg_sssp_kept_dag reads the reverse adjacency)
+    int64_t wdag_nv = -1, wdag_ne = 0;  // the held weighted predecessor DAG (Shard::wdag_*); -1: none
     int64_t census_listed = -1;       // the held component census (Shard::census_*); -1: none
     // the held PageRank top list (jg_pagerank_top, jg_top.hip; top_listed records in the list's order): the
     // caller-order index, rank and edgeCount of each, merged from the shards' selects and held on the host
@@ -580,6 +589,27 @@ void zero_gathered(const Graph& g, const Shard& sh, uint32_t adj, void* v, size_
 void graph_neighbors(const Graph& g, int direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                      int64_t* nbr_out);
 void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* dist_out);
+// jg_sssp_keep / jg_sssp_kept_row / jg_sssp_kept_release (jg_sssp.hip): one shard; the plane stays in
+// Shard::sssp_dist
+void sssp_keep(Graph& g, int64_t source_vid, int direction);
+void sssp_kept_row(Graph& g, int64_t* dist_out);
+void sssp_kept_release(Graph& g);
+// jg_sssp_kept_dag / jg_sssp_kept_dag_read (jg_pathdag.hip): the tight-edge predecessor DAG of the kept plane
+void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
+                   int64_t* farthest_out);
+void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
+                        int64_t* off_out, int32_t* pred_out);
+void sssp_kept_dag_drop(Graph& g);
+// The batches of the device-controlled loops (shortest distance's steps, the weighted DAG's rounds), whose
+// state the host reads once per batch: a first batch (the loop's own estimate), then 8, 16, ... 64 steps
+struct SdBatches {
+    int batch, next = 8;
+    int take() {
+        const int b = batch;
+        batch = next, next = std::min(next * 2, 64);
+        return b;
+    }
+};
 // labels_hook (nullable): called inside the timed region once the run's labels are final on shard 0's stream,
 // with the labelled rows' String-order ranks label[0, lrows); rows [lrows, rows) are edgeless and carry
 // their own rank (Shard::cc_rank0).  jg_cc_census counts from there.

@@ -21,6 +21,13 @@
 // across steps a wave-uniform carry, across ranges the sum of the per-range partial counts of the row
 // (dag_count_kernel leaves them; a 10^5-entry row spans ~100 ranges).  So a hub row is walked by many
 // lanes and waves and still emitted in row order.
+//
+// The weighted DAG of a kept distance plane (jg_sssp_kept_dag; DESIGN.md, "Weighted predecessor DAG on the
+// device") shares the emit: the count and fill passes are templates over the DAG's flavour (HopDag: depth
+// planes and "one level up"; TightDag: distance planes and "a tight edge"), which names the per-vertex value
+// and decides whether an entry counts.  Its sweep runs by rounds instead of levels (wdag_round_kernel).
+#include <climits>
+
 #include "jg_frontier.h"
 #include "jg_internal.h"
 
@@ -51,9 +58,11 @@ __global__ __launch_bounds__(kBlock) void dag_seed_kernel(const int32_t* __restr
     }
 }
 
-// key[j] = deepest - dep[idx[j]] (ascending keys = descending depth), val[j] = the row
-__global__ void dag_keys_kernel(const int64_t* __restrict__ idx, int64_t k, const int32_t* __restrict__ dep,
-                                int32_t deepest, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+// key[j] = deepest - dep[idx[j]] (ascending keys = descending depth), val[j] = the row (V: int32 depths, or
+// int64 distances with `deepest` the farthest one)
+template <class V>
+__global__ void dag_keys_kernel(const int64_t* __restrict__ idx, int64_t k, const V* __restrict__ dep,
+                                V deepest, uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < k; j += (int64_t)gridDim.x * blockDim.x) {
         const int64_t l = idx[j];
         key[j] = (uint64_t)(deepest - dep[l]);
@@ -153,13 +162,14 @@ __global__ __launch_bounds__(kBlock) void dag_step_kernel(DagStep a) {
 
 // The sorted DAG rows: local row, caller-order vertex, depth, and the row length the passes walk (0 for
 // the source: its predecessor range is empty).
+template <class V>
 __global__ void dag_unpack_kernel(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val, int64_t nv,
-                                  int32_t deepest, const int64_t* __restrict__ rp, const int32_t* __restrict__ dense,
+                                  V deepest, const int64_t* __restrict__ rp, const int32_t* __restrict__ dense,
                                   int32_t* __restrict__ local, int32_t* __restrict__ vertex,
-                                  int32_t* __restrict__ depth, int64_t* __restrict__ len) {
+                                  V* __restrict__ depth, int64_t* __restrict__ len) {
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nv; j += (int64_t)gridDim.x * blockDim.x) {
         const int32_t l = (int32_t)val[j];
-        const int32_t d = deepest - (int32_t)key[j];
+        const V d = deepest - (V)key[j];
         local[j] = l;
         vertex[j] = dense[l];
         depth[j] = d;
@@ -167,14 +177,45 @@ __global__ void dag_unpack_kernel(const uint64_t* __restrict__ key, const uint32
     }
 }
 
-struct DagWalk {
+// The two flavours of the emit passes.  Val: the per-vertex value (of the plane `dep` and of the sorted DAG
+// rows `depth`); Extra: what the predicate reads besides; counts(a, i, x, p, k): whether entry p of the
+// adjacency (column x, the k-th of its row) is listed as a predecessor of DAG row i.
+struct HopDag {  // jg_bfs_kept_dag: one level up, the first entry of its equal-column run
+    using Val = int32_t;
+    struct Extra {};
+    template <class W>
+    static __device__ __forceinline__ bool counts(const W& a, int64_t i, int32_t x, int64_t p, int64_t k) {
+        return a.dep[x] == a.depth[i] - 1 && (k == 0 || a.col[p - 1] != x);
+    }
+};
+struct TightDag {  // jg_sssp_kept_dag: a tight edge, the first of its weight in its equal-column run
+    using Val = long long;
+    struct Extra {
+        const int32_t* wt;
+    };
+    // All tight entries of one (v, u) run carry the run's smallest weight (a lighter one would have given v a
+    // smaller distance), so "the first tight entry of the run" is "tight, and no earlier entry of the run has
+    // this weight": a backward scan over the run's entries before p (parallel edges: a handful).
+    template <class W>
+    static __device__ __forceinline__ bool counts(const W& a, int64_t i, int32_t x, int64_t p, int64_t k) {
+        const int32_t w = a.wt[p];
+        const long long du = a.dep[x];
+        if (w == INT32_MIN || du == LLONG_MIN || du + (long long)w != a.depth[i]) return false;
+        for (int64_t q = p - 1; q >= p - k && a.col[q] == x; --q)
+            if (a.wt[q] == w) return false;
+        return true;
+    }
+};
+
+template <class T>
+struct DagWalk : T::Extra {
     const int32_t* local;   // [nv] DAG rows
-    const int32_t* depth;   // [nv]
+    const typename T::Val* depth;  // [nv]
     const int64_t* qoff;    // [nv + 1] first edge number of each DAG row (exclusive scan of the lengths)
     int64_t nv, mf, nranges;
     const int64_t* rp;
     const int32_t* col;
-    const int32_t* dep;
+    const typename T::Val* dep;
     const int32_t* dense;
     int32_t* cnt;           // [nv] distinct predecessors per DAG row (zeroed before the count pass)
     // per range: the DAG rows of its first and last entry, and the counted entries of each inside the range
@@ -191,7 +232,8 @@ struct DagLane {
     uint64_t mask;
     int lo;  // the row's first lane in this step
 };
-__device__ __forceinline__ DagLane dag_lane(const DagWalk& a, EdgeCursor& cur, int64_t sb, int64_t end) {
+template <class T>
+__device__ __forceinline__ DagLane dag_lane(const DagWalk<T>& a, EdgeCursor& cur, int64_t sb, int64_t end) {
     DagLane r{false, false, 0, 0, 0ull, 0};
     const int64_t e = sb + lane_id();
     r.valid = e < end;
@@ -201,7 +243,7 @@ __device__ __forceinline__ DagLane dag_lane(const DagWalk& a, EdgeCursor& cur, i
         const int64_t q0 = a.qoff[cur.i];
         const int64_t p = a.rp[a.local[cur.i]] + (e - q0);
         r.x = a.col[p];
-        r.counts = a.dep[r.x] == a.depth[cur.i] - 1 && (e == q0 || a.col[p - 1] != r.x);
+        r.counts = T::counts(a, cur.i, r.x, p, e - q0);
         const int64_t lo = q0 > sb ? q0 - sb : 0;
         const int64_t hi = cur.next_bound - sb < kWave ? cur.next_bound - sb : kWave;
         r.lo = (int)lo;
@@ -211,7 +253,8 @@ __device__ __forceinline__ DagLane dag_lane(const DagWalk& a, EdgeCursor& cur, i
     return r;
 }
 
-__global__ __launch_bounds__(kBlock) void dag_count_kernel(DagWalk a) {
+template <class T>
+__global__ __launch_bounds__(kBlock) void dag_count_kernel(DagWalk<T> a) {
     const int64_t nwaves = (int64_t)gridDim.x * (kBlock / kWave);
     for (int64_t w = (int64_t)blockIdx.x * (kBlock / kWave) + wave_id(); w < a.nranges; w += nwaves) {
         const int64_t base = w * kDagRange;
@@ -243,7 +286,8 @@ __global__ __launch_bounds__(kBlock) void dag_count_kernel(DagWalk a) {
     }
 }
 
-__global__ __launch_bounds__(kBlock) void dag_fill_kernel(DagWalk a) {
+template <class T>
+__global__ __launch_bounds__(kBlock) void dag_fill_kernel(DagWalk<T> a) {
     const int64_t nwaves = (int64_t)gridDim.x * (kBlock / kWave);
     for (int64_t w = (int64_t)blockIdx.x * (kBlock / kWave) + wave_id(); w < a.nranges; w += nwaves) {
         const int64_t base = w * kDagRange;
@@ -272,6 +316,122 @@ __global__ __launch_bounds__(kBlock) void dag_fill_kernel(DagWalk a) {
             open_row = __shfl(r.i, nvalid - 1, kWave);
         }
     }
+}
+
+// ---------------- the weighted DAG: seed and backward sweep by rounds ----------------
+
+// on[l] = row l is a target: a present distance, <= max_distance when that is >= 0, and its flag set;
+// *farthest = the largest distance of one (-1: none)
+__global__ __launch_bounds__(kBlock) void wdag_seed_kernel(const long long* __restrict__ dist,
+                                                           const int32_t* __restrict__ dense,
+                                                           const uint8_t* __restrict__ target, int64_t rows,
+                                                           long long max_distance, uint8_t* __restrict__ on,
+                                                           long long* __restrict__ farthest) {
+    __shared__ long long red[kBlock / kWave];
+    long long m = -1;
+    for (int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; l < rows; l += (int64_t)gridDim.x * blockDim.x) {
+        const long long d = dist[l];
+        const bool t = d != LLONG_MIN && (max_distance < 0 || d <= max_distance) && (!target || target[dense[l]] != 0);
+        on[l] = t ? 1 : 0;
+        if (t && d > m) m = d;
+    }
+    m = wave_reduce_max(m);
+    if (lane_id() == 0) red[wave_id()] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kBlock / kWave; ++w) m = red[w] > m ? red[w] : m;
+        if (m >= 0) atomicMax(farthest, m);
+    }
+}
+
+// Distances are not dense, so there are no levels to sweep: round 0's queue is every target, and round r
+// walks its queue's entries edge-parallel (as dag_step_kernel) and lists for round r + 1 each tight entry u
+// whose `on` byte it is first to set.  A row enters a queue once (a target's byte is set by the seed), so the
+// rounds' queues lie one after the other in one [rows] array and the work is the DAG rows' entries.  How many
+// rounds there are is not known up front: the host enqueues them in batches (SdBatches) and reads the ring
+// once per batch; a round whose queue has no entries returns at once, and so does every round after it.
+constexpr int kWdRing = 4;
+struct WdagRound {
+    const int64_t* rp;
+    const int32_t* col;
+    const int32_t* wt;
+    const long long* dist;
+    uint32_t* on;  // the `on` bytes as words (a byte is set with an atomic OR on its word)
+    int32_t* vq;   // [rows] the rounds' queues, concatenated
+    int64_t* qo;   // [rows + 1] each entry's first edge number inside its round
+    unsigned long long* packed;  // [kWdRing] round r's queue: (rows << kPackShift) | entries, slot r % kWdRing
+    int64_t* lbase;              // [kWdRing] its first queue slot
+    unsigned long long* rounds;  // rounds whose queue had rows
+    int32_t r;
+};
+
+// round 0's queue: the targets in row order, with their row lengths (scanned into qo by the host)
+__global__ void wdag_queue0_kernel(const int64_t* __restrict__ idx, int64_t nt, const int64_t* __restrict__ rp,
+                                   int32_t* __restrict__ vq, int64_t* __restrict__ len) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nt; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t l = idx[j];
+        vq[j] = (int32_t)l;
+        len[j] = rp[l + 1] - rp[l];
+    }
+}
+__global__ void wdag_ring0_kernel(WdagRound a, int64_t nt) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int k = 0; k < kWdRing; ++k) a.packed[k] = 0ull, a.lbase[k] = 0;
+        a.packed[0] = ((unsigned long long)nt << kPackShift) | (unsigned long long)a.qo[nt];
+        a.rounds[0] = 0ull;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void wdag_round_kernel(WdagRound a) {
+    __shared__ WaveStage ws;
+    const int cs = a.r % kWdRing, ns = (a.r + 1) % kWdRing;
+    const unsigned long long pk = a.packed[cs];
+    const int64_t nq = (int64_t)(pk >> kPackShift), mf = (int64_t)(pk & kEdgeMask);
+    const int64_t base = a.lbase[cs], nbase = base + nq;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.lbase[ns] = nbase;
+        a.packed[(a.r + 2) % kWdRing] = 0ull;  // round r + 1's output starts empty (no round reads or fills it now)
+        if (nq > 0) a.rounds[0] += 1;
+    }
+    if (mf == 0) return;  // (grid-uniform) nothing left to walk: this round and every later one
+    WaveApp app{ws};
+    const int32_t* queue = a.vq + base;
+    const int64_t* qoff = a.qo + base;
+    int32_t* qout = a.vq + nbase;
+    int64_t* qoout = a.qo + nbase;
+    unsigned long long* pout = a.packed + ns;
+    const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t per_tile = nthreads * 4;
+    const int64_t tiles = (mf + per_tile - 1) / per_tile;
+    for (int64_t t = 0; t < tiles; ++t) {
+        if ((t * nthreads + (int64_t)blockIdx.x * blockDim.x) * 4 >= mf) break;  // block-uniform
+        const int64_t e0 = (t * nthreads + tid) * 4;
+        EdgeCursor cur{qoff, nq, mf};
+        if (e0 < mf) cur.seek(e0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t e = e0 + k;
+            bool take = false;
+            int32_t u = 0;
+            int64_t deg = 0;
+            if (e < mf) {
+                cur.advance(e);
+                const int32_t v = queue[cur.i];
+                const int64_t j = a.rp[v] + cur.row_offset(e);
+                u = a.col[j];
+                const int32_t w = a.wt[j];
+                const long long du = a.dist[u];
+                if (w != INT32_MIN && du != LLONG_MIN && du + (long long)w == a.dist[v]) {
+                    const uint32_t bit = 1u << ((u & 3) * 8);
+                    if (!(a.on[u >> 2] & bit)) take = !(atomicOr(&a.on[u >> 2], bit) & bit);
+                    if (take) deg = a.rp[u + 1] - a.rp[u];
+                }
+            }
+            app.append(take, u, deg, qout, qoout, pout);
+        }
+    }
+    app.final(qout, qoout, pout);
 }
 
 const Csr& reverse_csr(const Shard& sh, int dir) {
@@ -356,7 +516,7 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     const int dbits = std::max(bits_for((uint64_t)deepest), 1);
     DevBuf<uint64_t> tkey((size_t)nt);
     DevBuf<uint32_t> tval((size_t)nt);
-    dag_keys_kernel<<<grid_for(nt), kBlock, 0, st>>>(idx.get(), nt, dep, deepest, tkey.get(), tval.get());
+    dag_keys_kernel<int32_t><<<grid_for(nt), kBlock, 0, st>>>(idx.get(), nt, dep, deepest, tkey.get(), tval.get());
     JG_LAUNCH_CHECK();
     prim::radix_sort(tkey.get(), tval.get(), nt, dbits, st);
 
@@ -381,7 +541,7 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     const int64_t nv = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
     DevBuf<uint64_t> vkey((size_t)nv);
     DevBuf<uint32_t> vval((size_t)nv);
-    dag_keys_kernel<<<grid_for(nv), kBlock, 0, st>>>(idx.get(), nv, dep, deepest, vkey.get(), vval.get());
+    dag_keys_kernel<int32_t><<<grid_for(nv), kBlock, 0, st>>>(idx.get(), nv, dep, deepest, vkey.get(), vval.get());
     JG_LAUNCH_CHECK();
     prim::radix_sort(vkey.get(), vval.get(), nv, dbits, st);
     DevBuf<int32_t> local((size_t)nv);
@@ -389,9 +549,9 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     sh.dag_vertex.alloc((size_t)nv);
     sh.dag_depth.alloc((size_t)nv);
     sh.dag_off.alloc((size_t)nv + 1);
-    dag_unpack_kernel<<<grid_for(nv), kBlock, 0, st>>>(vkey.get(), vval.get(), nv, deepest, c.row_ptr.get(),
-                                                       sh.dense_rows.get(), local.get(), sh.dag_vertex.get(),
-                                                       sh.dag_depth.get(), len.get());
+    dag_unpack_kernel<int32_t><<<grid_for(nv), kBlock, 0, st>>>(vkey.get(), vval.get(), nv, deepest, c.row_ptr.get(),
+                                                                sh.dense_rows.get(), local.get(), sh.dag_vertex.get(),
+                                                                sh.dag_depth.get(), len.get());
     JG_LAUNCH_CHECK();
     prim::exclusive_scan(len.get(), qoff.get(), nv, st);
     int64_t mf = 0;
@@ -401,11 +561,11 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
     DevBuf<int32_t> rfi((size_t)std::max<int64_t>(nranges, 1)), rli((size_t)std::max<int64_t>(nranges, 1)),
         rca((size_t)std::max<int64_t>(nranges, 1)), rcl((size_t)std::max<int64_t>(nranges, 1));
-    DagWalk wk{local.get(), sh.dag_depth.get(), qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(), dep,
-               sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr, nullptr};
+    DagWalk<HopDag> wk{{}, local.get(), sh.dag_depth.get(), qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(), dep,
+                       sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr, nullptr};
     const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
     if (mf > 0) {
-        dag_count_kernel<<<walk_grid, kBlock, 0, st>>>(wk);
+        dag_count_kernel<HopDag><<<walk_grid, kBlock, 0, st>>>(wk);
         JG_LAUNCH_CHECK();
         ++launches;
     }
@@ -416,7 +576,7 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     if (mf > 0) {
         wk.off = sh.dag_off.get();
         wk.pred = sh.dag_pred.get();
-        dag_fill_kernel<<<walk_grid, kBlock, 0, st>>>(wk);
+        dag_fill_kernel<HopDag><<<walk_grid, kBlock, 0, st>>>(wk);
         JG_LAUNCH_CHECK();
         ++launches;
     }
@@ -456,6 +616,198 @@ void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_o
         copy_d2h(&b, sh.dag_off.get() + first, sizeof(int64_t), st);
         copy_d2h(&e, sh.dag_off.get() + first + count, sizeof(int64_t), st);
         copy_d2h(pred_out, sh.dag_pred.get() + b, (size_t)(e - b) * sizeof(int32_t), st);
+    }
+}
+
+void sssp_kept_dag_drop(Graph& g) {
+    for (auto& sp : g.shards) {
+        DeviceGuard dg(*sp);
+        sp->wdag_vertex.reset();
+        sp->wdag_dist.reset();
+        sp->wdag_pred.reset();
+        sp->wdag_off.reset();
+    }
+    g.wdag_nv = -1;
+    g.wdag_ne = 0;
+}
+
+void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
+                   int64_t* farthest_out) {
+    if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag runs on one shard");
+    if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep)");
+    Shard& sh = *g.shards[0];
+    const Csr& c = reverse_csr(sh, g.sssp_dir);
+    if (!c.present() || c.weight.size() == 0)
+        fail(JG_ERR_UNSUPPORTED,
+             "jg_sssp_kept_dag reads the reverse of the kept direction's adjacency: not built, or built without weights");
+    if (sh.rows != g.n || sh.dense_rows.size() < (size_t)std::max<int64_t>(sh.rows, 1))
+        fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag: the shard does not hold every vertex");
+    if (sh.rows >> (64 - kPackShift)) fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag: too many rows for the round counters");
+    sssp_kept_dag_drop(g);
+    Ctx& ctx = *g.ctx;
+    ctx.last = jg_stats{};
+    DeviceGuard dg(sh);
+    hipStream_t st = sh.stream;
+    const int64_t rows = sh.rows;
+    const long long* dist = sh.sssp_dist.get();
+    const auto finish = [&](int64_t nv, int64_t ne, int64_t farthest, int64_t rounds) {
+        g.wdag_nv = nv;
+        g.wdag_ne = ne;
+        if (nv_out) *nv_out = nv;
+        if (ne_out) *ne_out = ne;
+        if (farthest_out) *farthest_out = farthest;
+        ctx.last.levels = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+        ctx.last.supersteps = ctx.last.levels;
+    };
+    if (rows == 0) return finish(0, 0, -1, 0);
+
+    DevBuf<uint8_t> dtarget;
+    if (target) {  // the mask travels before the timed region
+        dtarget.alloc((size_t)g.n);
+        copy_h2d(dtarget.get(), target, (size_t)g.n, st);
+    }
+    Event t0, t1;
+    JG_HIP(hipEventRecord(t0, st));
+
+    // ---- seed ----
+    const int64_t on_words = (rows + 3) / 4;
+    DevBuf<uint32_t> on((size_t)on_words);
+    DevBuf<long long> d_far(1);
+    JG_HIP(hipMemsetAsync(on.get(), 0, on.bytes(), st));
+    JG_HIP(hipMemsetAsync(d_far.get(), 0xff, sizeof(long long), st));
+    uint8_t* on8 = reinterpret_cast<uint8_t*>(on.get());
+    wdag_seed_kernel<<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(dist, sh.dense_rows.get(), dtarget.get(), rows,
+                                                                     (long long)max_distance, on8, d_far.get());
+    JG_LAUNCH_CHECK();
+    DevBuf<int64_t> idx((size_t)rows), cpos, cscan;
+    const int64_t nt = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
+    if (nt == 0) {
+        JG_HIP(hipEventRecord(t1, st));
+        JG_HIP(hipEventSynchronize(t1));
+        float ms = 0;
+        JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+        finish(0, 0, -1, 0);
+        ctx.last.compute_ms = ms;
+        ctx.last.algorithmic_bytes = 14.0 * (double)rows;
+        return;
+    }
+    long long farthest = -1;
+    copy_d2h(&farthest, d_far.get(), sizeof(long long), st);
+    const int dbits = std::max(bits_for((uint64_t)farthest), 1);
+
+    // ---- backward sweep by rounds ----
+    DevBuf<int32_t> vq((size_t)rows);
+    DevBuf<int64_t> qo((size_t)rows + 1), len((size_t)rows);
+    DevBuf<unsigned long long> ring((size_t)kWdRing + 1);
+    DevBuf<int64_t> lbase((size_t)kWdRing);
+    WdagRound rd{c.row_ptr.get(), c.col.get(), c.weight.get(), dist, on.get(), vq.get(), qo.get(), ring.get(),
+                 lbase.get(), ring.get() + kWdRing, 0};
+    wdag_queue0_kernel<<<grid_for(nt), kBlock, 0, st>>>(idx.get(), nt, c.row_ptr.get(), vq.get(), len.get());
+    JG_LAUNCH_CHECK();
+    prim::exclusive_scan(len.get(), qo.get(), nt, st);
+    wdag_ring0_kernel<<<1, kWave, 0, st>>>(rd, nt);
+    JG_LAUNCH_CHECK();
+    const unsigned round_grid = grid_for(std::max<int64_t>(c.nnz / 4, rows), kBlock, 1024);
+    int32_t r = 0;
+    unsigned long long pk = 0;  // round r's queue (the first not yet enqueued): no entries = nothing left
+    for (SdBatches b{16};;) {
+        if (r > (1 << 30)) fail(JG_ERR_STATE, "the weighted DAG's round control did not terminate");
+        for (int k = 0, batch = b.take(); k < batch; ++k, ++r) {
+            rd.r = r;
+            wdag_round_kernel<<<round_grid, kBlock, 0, st>>>(rd);
+            JG_LAUNCH_CHECK();
+        }
+        copy_d2h(&pk, ring.get() + r % kWdRing, sizeof pk, st);
+        if ((pk & kEdgeMask) == 0) break;
+    }
+    int64_t launches = r;
+    unsigned long long rounds = 0;  // rounds whose queue had rows: the launched ones', and a last edgeless queue
+    copy_d2h(&rounds, ring.get() + kWdRing, sizeof rounds, st);
+    if ((pk >> kPackShift) > 0) ++rounds;
+
+    // ---- emit (the passes of the hop DAG, with the tight-edge predicate) ----
+    const int64_t nv = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
+    DevBuf<uint64_t> vkey((size_t)nv);
+    DevBuf<uint32_t> vval((size_t)nv);
+    dag_keys_kernel<long long><<<grid_for(nv), kBlock, 0, st>>>(idx.get(), nv, dist, farthest, vkey.get(), vval.get());
+    JG_LAUNCH_CHECK();
+    prim::radix_sort(vkey.get(), vval.get(), nv, dbits, st);
+    DevBuf<int32_t> local((size_t)nv);
+    DevBuf<int64_t> rlen((size_t)nv), qoff((size_t)nv + 1);
+    sh.wdag_vertex.alloc((size_t)nv);
+    sh.wdag_dist.alloc((size_t)nv);
+    sh.wdag_off.alloc((size_t)nv + 1);
+    long long* wd = reinterpret_cast<long long*>(sh.wdag_dist.get());
+    dag_unpack_kernel<long long><<<grid_for(nv), kBlock, 0, st>>>(vkey.get(), vval.get(), nv, farthest, c.row_ptr.get(),
+                                                                  sh.dense_rows.get(), local.get(),
+                                                                  sh.wdag_vertex.get(), wd, rlen.get());
+    JG_LAUNCH_CHECK();
+    prim::exclusive_scan(rlen.get(), qoff.get(), nv, st);
+    int64_t mf = 0;
+    copy_d2h(&mf, qoff.get() + nv, sizeof(int64_t), st);
+    DevBuf<int32_t> cnt((size_t)nv);
+    JG_HIP(hipMemsetAsync(cnt.get(), 0, cnt.bytes(), st));
+    const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
+    const size_t nr = (size_t)std::max<int64_t>(nranges, 1);
+    DevBuf<int32_t> rfi(nr), rli(nr), rca(nr), rcl(nr);
+    DagWalk<TightDag> wk{{c.weight.get()}, local.get(), wd, qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(),
+                         dist, sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr,
+                         nullptr};
+    const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
+    if (mf > 0) {
+        dag_count_kernel<TightDag><<<walk_grid, kBlock, 0, st>>>(wk);
+        JG_LAUNCH_CHECK();
+        ++launches;
+    }
+    prim::exclusive_scan(cnt.get(), sh.wdag_off.get(), nv, st);
+    int64_t ne = 0;
+    copy_d2h(&ne, sh.wdag_off.get() + nv, sizeof(int64_t), st);
+    sh.wdag_pred.alloc((size_t)std::max<int64_t>(ne, 1));
+    if (mf > 0) {
+        wk.off = sh.wdag_off.get();
+        wk.pred = sh.wdag_pred.get();
+        dag_fill_kernel<TightDag><<<walk_grid, kBlock, 0, st>>>(wk);
+        JG_LAUNCH_CHECK();
+        ++launches;
+    }
+    JG_HIP(hipEventRecord(t1, st));
+    JG_HIP(hipEventSynchronize(t1));
+    float ms = 0;
+    JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    finish(nv, ne, farthest, (int64_t)rounds);
+    ctx.last.compute_ms = ms;
+    ctx.last.kernel_launches = launches;
+    ctx.last.edges_traversed = (double)mf;
+    // Byte model, as the hop DAG's with 8-byte distances and the weights.  Seed and the two compactions: 14 B
+    // per row (distance, dense index, mask and `on` byte), 9 B per row per compaction (flag + position).  Each
+    // of the three walks (sweep, count, fill) reads a DAG-row entry's column (4 B) and weight (4 B) and probes
+    // its distance (8 B): 3 x 16 B per entry (the sweep also walks the source's row when it is a target, the
+    // backward scan over a run of parallel edges re-reads cached lines: neither is counted).  A DAG vertex costs
+    // ~72 B (two sort records of 12 B read and written, queue entry, row_ptr pair, count, offset, the 8-byte
+    // distance and the other outputs), an emitted predecessor 8 B (dense probe + store).
+    ctx.last.algorithmic_bytes = 32.0 * (double)rows + 48.0 * (double)mf + 72.0 * (double)nv + 8.0 * (double)ne;
+}
+
+void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
+                        int64_t* off_out, int32_t* pred_out) {
+    if (g.wdag_nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag)");
+    if (first < 0 || count < 0 || first > g.wdag_nv || count > g.wdag_nv - first)
+        fail(JG_ERR_ARG, "range outside the DAG's vertices");
+    if (g.wdag_nv == 0) {
+        if (off_out) off_out[0] = 0;
+        return;
+    }
+    Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    hipStream_t st = sh.stream;
+    if (vertex_out) copy_d2h(vertex_out, sh.wdag_vertex.get() + first, (size_t)count * sizeof(int32_t), st);
+    if (dist_out) copy_d2h(dist_out, sh.wdag_dist.get() + first, (size_t)count * sizeof(int64_t), st);
+    if (off_out) copy_d2h(off_out, sh.wdag_off.get() + first, (size_t)(count + 1) * sizeof(int64_t), st);
+    if (pred_out) {
+        int64_t b = 0, e = 0;
+        copy_d2h(&b, sh.wdag_off.get() + first, sizeof(int64_t), st);
+        copy_d2h(&e, sh.wdag_off.get() + first + count, sizeof(int64_t), st);
+        copy_d2h(pred_out, sh.wdag_pred.get() + b, (size_t)(e - b) * sizeof(int32_t), st);
     }
 }
 

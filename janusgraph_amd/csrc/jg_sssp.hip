@@ -10,6 +10,9 @@
 //   (messages of superstep t-1 only: push over the in-CSR with 64-bit atomicMin into a scratch array, then
 //   apply), on one shard or sharded over the IN halo plan; delta-stepping when the hop bound cannot bind
 //   and no weight is negative; unit weights on one shard: the DO-BFS of jg_traverse.hip (bfs_in_depths).
+// jg_sssp_keep (sssp_keep, at the end): the delta-stepping engine over the adjacency of a direction, its
+//   distances left on the device for the weighted predecessor DAG of jg_pathdag.hip (ShortestPathVertexProgram
+//   with a distanceProperty).
 #include <climits>
 #include <cmath>
 
@@ -239,7 +242,9 @@ struct SdStep {
     D* dist;                    // DistTraits<D>::kNone: unreached
     int32_t* nq[2];             // near queues: step s relaxes nq[s & 1] (and its first-edge offsets qo),
     int64_t* qo[2];             // its near pass appends to nq[(s + 1) & 1]
-    unsigned long long* nctr;   // [kSdRing] step s's near queue, packed (rows << kPackShift) | edges
+    unsigned long long* nctr;   // [kSdRing] step s's near queue as the near pass before it left it, packed
+                                //   (rows << kPackShift) | edges
+    unsigned long long* sctr;   // [kSdRing] the near queue step s's split filled instead (same packing)
     int32_t* far[2];            // far piles and their sizes
     unsigned long long* fsz;    // [2]
     int32_t* far_flag;
@@ -252,11 +257,16 @@ struct SdStep {
     int32_t step;
 };
 
-// Step s's decision (every block of both kernels computes it from the same completed inputs): relax the
-// near queue when it has entries; else stop when the far pile is empty; else move the far pile, with the
-// threshold past the previous one by delta, or to the bucket of the smallest far distance seen when that
-// lies further (the host version's two split attempts; any threshold sequence gives the same distances,
-// the bucket only decides how much is relaxed again)
+// Step s's decision: relax the near queue when it has entries; else stop when the far pile is empty; else
+// move the far pile, with the threshold past the previous one by delta, or to the bucket of the smallest far
+// distance seen when that lies further (the host version's two split attempts; any threshold sequence gives
+// the same distances, the bucket only decides how much is relaxed again).
+// Invariant: the decision reads only what no kernel of step s writes, so every workgroup of
+// sd_split_kernel computes the same one however late it starts: st[s - 1] and fmin[s - 1] (step s - 1's),
+// nctr[s] (appended to by step s - 1's near pass alone; step s's split appends to sctr[s], which is not read
+// here), and fsz[p.fc] (step s's split appends to fsz[p.fc ^ 1]; its near pass runs after every split
+// workgroup has decided).  A split that appended to nctr[s] let a late workgroup see entries, decide
+// "no split" and leave its part of the far pile where it was.
 template <class D>
 __device__ SdState sd_decide(const SdStep<D>& a) {
     const int ps = (a.step + kSdRing - 1) % kSdRing;
@@ -304,7 +314,7 @@ __global__ __launch_bounds__(kBlock) void sd_split_kernel(SdStep<D> a) {
     const long long T = s_st.T, t_prev = s_tprev;
     int32_t* nq = a.nq[a.step & 1];
     int64_t* qo = a.qo[a.step & 1];
-    unsigned long long* packed = a.nctr + a.step % kSdRing;
+    unsigned long long* packed = a.sctr + a.step % kSdRing;  // not nctr: sd_decide reads that one
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     unsigned long long mk = ULLONG_MAX;
     for (int64_t x0 = (int64_t)blockIdx.x * blockDim.x; x0 < fsize; x0 += stride) {  // block-uniform trips
@@ -334,9 +344,11 @@ __global__ __launch_bounds__(kBlock) void sd_split_kernel(SdStep<D> a) {
 }
 
 // One near pass, edge-balanced over the step's near queue (first-edge numbers, one binary search per 4
-// edges per thread).  Block 0 also keeps the rings: the next step's output counter and far minimum start
-// empty, the far minimum carries over a step without a split, and after a split the emptied pile's size
-// is reset.
+// edges per thread): after a split the queue the split filled (sctr; the rows the pass before left in nctr
+// have no entries, or the step would not have split, so the split wrote over them from slot 0 and only their
+// count is kept, for `passes`).  Block 0 also keeps the rings: the next step's output counters and far
+// minimum start empty, the far minimum carries over a step without a split, and after a split the emptied
+// pile's size is reset.
 template <class D>
 __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
     __shared__ SdState s_st;
@@ -345,15 +357,17 @@ __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
     const int cs = a.step % kSdRing;
     if (threadIdx.x == 0) {
         s_st = a.st[cs];
-        const unsigned long long h = a.nctr[cs];
+        const unsigned long long h = s_st.split ? a.sctr[cs] : a.nctr[cs];
         s_nq = (long long)(h >> kPackShift);
         s_mf = (long long)(h & kEdgeMask);
+        const long long left = s_st.split ? (long long)(a.nctr[cs] >> kPackShift) : 0;  // edgeless rows
         if (blockIdx.x == 0 && !s_st.done) {
             a.nctr[(a.step + 2) % kSdRing] = 0ull;
+            a.sctr[(a.step + 2) % kSdRing] = 0ull;
             a.fmin[(a.step + 2) % kSdRing] = ULLONG_MAX;
             if (s_st.split) a.fsz[s_st.fc ^ 1] = 0ull;
             else atomicMin(a.fmin + cs, a.fmin[(a.step + kSdRing - 1) % kSdRing]);
-            if (s_nq > 0) a.passes[0] += 1;  // (as the host-driven passes counted: a queue with rows)
+            if (s_nq + left > 0) a.passes[0] += 1;  // (as the host-driven passes counted: a queue with rows)
         }
     }
     __syncthreads();
@@ -438,6 +452,7 @@ __global__ void sd_init_kernel(SdStep<D> a, int64_t rows, int32_t seed, long lon
         a.qo[0][0] = 0;
         a.nctr[0] = (1ull << kPackShift) | (unsigned long long)(a.rp[seed + 1] - a.rp[seed]);
         for (int k = 1; k < kSdRing; ++k) a.nctr[k] = 0ull;
+        for (int k = 0; k < kSdRing; ++k) a.sctr[k] = 0ull;
         for (int k = 0; k < kSdRing; ++k) a.fmin[k] = ULLONG_MAX;
         a.fsz[0] = a.fsz[1] = 0ull;
         a.passes[0] = 0ull;
@@ -551,17 +566,6 @@ struct SdSuperBufs {
         for (int k = 0; k < 2; ++k) frontier[k].alloc(cap), qoff[k].alloc(cap);
         touched.alloc(cap);
         err.alloc(1);
-    }
-};
-
-// The batches of the device-controlled loops, whose state the host reads once per batch: a first batch
-// (the loop's own estimate), then 8, 16, ... 64 steps
-struct SdBatches {
-    int batch, next = 8;
-    int take() {
-        const int b = batch;
-        batch = next, next = std::min(next * 2, 64);
-        return b;
     }
 };
 
@@ -746,20 +750,31 @@ long long sd_auto_delta(const long long* ws, int64_t nnz, int64_t rows) {
     return std::max<long long>(1, (long long)std::llround(kSdDeltaScale * mean_w / mean_deg));
 }
 
-// Near-far delta-stepping from `seed` over sh.in (see sd_near_kernel); host[] gets the distances
-// (INT64_MIN: absent); end_ev is recorded once the distances are final, before they are copied out.
-// Returns the near passes run.
+// The kept plane of a run (jg_sssp_keep): int64 in local row order, LLONG_MIN where the run's own plane has
+// "unreached"
 template <class D>
-int sd_delta_stepping_t(Shard& sh, int64_t seed, long long delta, int64_t* host, hipEvent_t end_ev) {
+__global__ void sd_widen_kernel(const D* __restrict__ dist, int64_t rows, long long* __restrict__ plane) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
+        const D d = dist[i];
+        plane[i] = d == DistTraits<D>::kNone ? LLONG_MIN : (long long)d;
+    }
+}
+
+// Near-far delta-stepping from `seed` over the rows of c (an adjacency of sh: a row's entries are the rows
+// it relaxes; see sd_near_kernel).  host[] (nullable) gets the distances (INT64_MIN: absent), plane
+// (nullable, on the device, [rows]) the same in local row order, written before end_ev; end_ev is recorded
+// once the distances are final, before they are copied out.  Returns the near passes run.
+template <class D>
+int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, long long delta, int64_t* host, long long* plane,
+                        hipEvent_t end_ev) {
     hipStream_t s = sh.stream;
     const int64_t rows = sh.rows, cap = std::max<int64_t>(rows, 1);
-    const Csr& c = sh.in;
     DevBuf<D> dist(cap);
     DevBuf<int32_t> nq[2] = {DevBuf<int32_t>(cap), DevBuf<int32_t>(cap)};
     DevBuf<int64_t> qo[2] = {DevBuf<int64_t>(cap), DevBuf<int64_t>(cap)};
     DevBuf<int32_t> far[2] = {DevBuf<int32_t>(cap), DevBuf<int32_t>(cap)};
     DevBuf<int32_t> stamp(cap), far_flag(cap), err(1);
-    DevBuf<unsigned long long> ring(2 * kSdRing + 3);  // nctr[kSdRing], fmin[kSdRing], fsz[2], passes
+    DevBuf<unsigned long long> ring(3 * kSdRing + 3);  // nctr[kSdRing], fmin[kSdRing], fsz[2], passes, sctr[kSdRing]
     DevBuf<SdState> st(kSdRing);
     SdStep<D> a{};
     a.rp = c.row_ptr.get();
@@ -775,6 +790,7 @@ int sd_delta_stepping_t(Shard& sh, int64_t seed, long long delta, int64_t* host,
     a.fmin = ring.get() + kSdRing;
     a.fsz = ring.get() + 2 * kSdRing;
     a.passes = ring.get() + 2 * kSdRing + 2;
+    a.sctr = ring.get() + 2 * kSdRing + 3;
     a.far_flag = far_flag.get();
     a.stamp = stamp.get();
     a.st = st.get();
@@ -805,6 +821,10 @@ int sd_delta_stepping_t(Shard& sh, int64_t seed, long long delta, int64_t* host,
         copy_d2h(&hs, st.get() + (step - 1) % kSdRing, sizeof hs, s);
         if (hs.done) break;
     }
+    if (plane && rows) {
+        sd_widen_kernel<D><<<grid_for(rows), kBlock, 0, s>>>(dist.get(), rows, plane);
+        JG_LAUNCH_CHECK();
+    }
     JG_HIP(hipEventRecord(end_ev, s));  // the distances are final: their copy-out is the caller's
     region_mark(s, false);
     unsigned long long passes = 0;
@@ -813,9 +833,11 @@ int sd_delta_stepping_t(Shard& sh, int64_t seed, long long delta, int64_t* host,
     for (int k = 3; k > 0; --k) sh.sd_hist[k] = sh.sd_hist[k - 1];
     sh.sd_hist[0] = hs.end_step + 1;
     sh.sd_hist_n = std::min(sh.sd_hist_n + 1, 4);
-    std::vector<D> hd(rows);
-    if (rows) copy_d2h(hd.data(), dist.get(), rows * sizeof(D), s);
-    for (int64_t l = 0; l < rows; ++l) host[l] = hd[l] == DistTraits<D>::kNone ? LLONG_MIN : (int64_t)hd[l];
+    if (host) {
+        std::vector<D> hd(rows);
+        if (rows) copy_d2h(hd.data(), dist.get(), rows * sizeof(D), s);
+        for (int64_t l = 0; l < rows; ++l) host[l] = hd[l] == DistTraits<D>::kNone ? LLONG_MIN : (int64_t)hd[l];
+    }
     int32_t e = 0;
     copy_d2h(&e, err.get(), sizeof e, s);
     if (e) fail(JG_ERR_ARG, kMissingWeight);
@@ -829,13 +851,14 @@ int sd_delta_stepping_t(Shard& sh, int64_t seed, long long delta, int64_t* host,
 // RMAT-20 1.197 / 1.249, RMAT-22 3.036 / 3.130, RMAT-24 10.715 / 10.228 (fabric reads -18% at RMAT-22, but
 // the near pass is bound by its random round trips and atomics more than by the lines they move;
 // profiles/r06/sssp32/)
-int sd_delta_stepping(Shard& sh, int64_t seed, long long delta, int64_t* host, hipEvent_t end_ev, const long long* ws) {
+int sd_delta_stepping(Shard& sh, const Csr& c, int64_t seed, long long delta, int64_t* host, long long* plane,
+                      hipEvent_t end_ev, const long long* ws) {
     const unsigned long long wmax = ws[3] > 0 ? (unsigned long long)ws[3] : 0ull;
     const unsigned long long bound = (unsigned long long)std::max<int64_t>(sh.rows, 1) * wmax;  // rows * wmax
     const bool want32 = tune().sd_dist32 == 2 || (tune().sd_dist32 == 1 && sh.rows >= (1ll << 23));
     if (want32 && wmax < (1ull << 31) && (uint64_t)sh.rows < (1ull << 32) && bound < (unsigned long long)UINT_MAX)
-        return sd_delta_stepping_t<unsigned int>(sh, seed, delta, host, end_ev);
-    return sd_delta_stepping_t<long long>(sh, seed, delta, host, end_ev);
+        return sd_delta_stepping_t<unsigned int>(sh, c, seed, delta, host, plane, end_ev);
+    return sd_delta_stepping_t<long long>(sh, c, seed, delta, host, plane, end_ev);
 }
 
 // The hop-bounded supersteps from `seed` over sh.in (sd_push_q_kernel + sd_apply_q_kernel per superstep);
@@ -924,7 +947,7 @@ void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* d
         if (rows) copy_d2h(h.data(), depth.get(), rows * sizeof(int32_t), s);
         for (int64_t l = 0; l < rows; ++l) host[l] = h[l] >= 0 ? h[l] : LLONG_MIN;
     } else if (delta > 0) {
-        levels = sd_delta_stepping(sh, seed, delta, host.data(), t1, sd_weight_stats(sh, sh.in));
+        levels = sd_delta_stepping(sh, sh.in, seed, delta, host.data(), nullptr, t1, sd_weight_stats(sh, sh.in));
     } else {
         levels = sd_supersteps(sh, seed, max_depth, host.data(), t1);
     }
@@ -936,6 +959,73 @@ void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* d
     ctx.last.supersteps = max_depth;  // Fulgora always runs supersteps 0..maxDepth
     for (int64_t l = 0; l < rows; ++l) dist_out[sh.dense_of_local()[l]] = host[l];
     prof_collect(ctx, g);
+}
+
+// ---------------- jg_sssp_keep: the distances stay on the device ----------------
+
+void sssp_kept_release(Graph& g) {
+    sssp_kept_dag_drop(g);
+    for (auto& sp : g.shards) {
+        DeviceGuard dg(*sp);
+        sp->sssp_dist.reset();
+    }
+    g.sssp_kept = false;
+}
+
+// Shortest summed weights from one source along `direction`, by the delta-stepping of jg_shortest_distance
+// over the adjacency whose rows hold the edges followed (OUT: sh.out, IN: sh.in, BOTH: the weighted sh.both);
+// the int64 plane stays in Shard::sssp_dist for jg_sssp_kept_row and jg_sssp_kept_dag.
+void sssp_keep(Graph& g, int64_t source_vid, int direction) {
+    if (direction < JG_DIR_OUT || direction > JG_DIR_BOTH) fail(JG_ERR_ARG, "bad direction");
+    if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_sssp_keep runs on one shard");
+    sssp_kept_release(g);
+    Ctx& ctx = *g.ctx;
+    ctx.last = jg_stats{};
+    Shard& sh = *g.shards[0];
+    const Csr& c = direction == JG_DIR_BOTH ? sh.both : direction == JG_DIR_OUT ? sh.out : sh.in;
+    if (!g.has_weights) fail(JG_ERR_UNSUPPORTED, "jg_sssp_keep needs a graph built with edge weights");
+    if (!c.present() || c.weight.size() == 0)
+        fail(JG_ERR_UNSUPPORTED, direction == JG_DIR_BOTH
+                                     ? "jg_sssp_keep over JG_DIR_BOTH needs JG_ADJ_BOTH | JG_ADJ_WEIGHT_BOTH at build time"
+                                     : "jg_sssp_keep: the adjacency of that direction was not built with weights");
+    DeviceGuard dg(sh);
+    hipStream_t s = sh.stream;
+    const int64_t rows = sh.rows;
+    // the weight statistics are taken once per adjacency, outside the timed region
+    const long long* ws = sd_weight_stats(sh, c);
+    if (ws[2] > 0 && ws[0] < 1)
+        fail(JG_ERR_ARG, "jg_sssp_keep needs weights >= 1 (a zero-weight edge makes the tight-edge graph cyclic)");
+    int shard = 0;
+    const int64_t seed = local_of_vid(g, source_vid, &shard);
+    DevBuf<long long> plane((size_t)std::max<int64_t>(rows, 1));
+    Event t0, t1;
+    region_mark(s, true);
+    JG_HIP(hipEventRecord(t0, s));
+    int levels = 0;
+    if (seed < 0) {  // not a vertex: every distance absent
+        if (rows) {
+            fill_ll_kernel<<<grid_for(rows), kBlock, 0, s>>>(plane.get(), rows, LLONG_MIN);
+            JG_LAUNCH_CHECK();
+        }
+        JG_HIP(hipEventRecord(t1, s));
+        region_mark(s, false);
+    } else {
+        levels = sd_delta_stepping(sh, c, seed, sd_auto_delta(ws, c.nnz, rows), nullptr, plane.get(), t1, ws);
+    }
+    JG_HIP(hipEventSynchronize(t1));
+    float ms = 0;
+    JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    ctx.last.compute_ms = ms;
+    ctx.last.levels = levels;
+    sh.sssp_dist.swap(plane);
+    g.sssp_kept = true;
+    g.sssp_dir = direction;
+}
+
+void sssp_kept_row(Graph& g, int64_t* dist_out) {
+    if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep)");
+    Shard& sh = *g.shards[0];
+    rows_to_dense(g, sh, sh.sssp_dist.get(), reinterpret_cast<long long*>(dist_out));
 }
 
 }  // namespace jg

@@ -147,9 +147,17 @@ class ConnectedComponentVertexProgram(VertexProgram):
 
 
 class ShortestPathVertexProgram(VertexProgram):
-    """Depth on the GPU (Fulgora forces {Local(bothE), Global}), paths rebuilt on the host."""
+    """Depth on the GPU (Fulgora forces {Local(bothE), Global}), paths rebuilt on the host.
+
+    TinkerPop's two further knobs [TP-recall]: distanceProperty(key) makes a path's length the sum of that edge
+    property (Integer, >= 1 here: anything else is refused with ProgramNotSupported at submit), and maxDistance
+    then bounds that sum, inclusive; edgeDirection("out" | "in" | "both") restricts the edges a path follows
+    (default "both").  memory.getIteration() is 1 + the number of edges of the longest returned path (1 when
+    there is none), with or without a distance property: this project's rule, not pinned by any reference
+    test."""
 
     SHORTEST_PATHS = "gremlin.shortestPathVertexProgram.shortestPaths"
+    EDGE_DIRECTIONS = ("out", "in", "both")
     preferred_persist = Persist.NOTHING
 
     def load_state(self, conf):
@@ -159,6 +167,13 @@ class ShortestPathVertexProgram(VertexProgram):
         self.include_edges = bool(conf.get("includeEdges", False))
         if self.include_edges:
             raise ValueError("includeEdges is not supported by GpuGraphComputer")
+        self.distance_property = conf.get("distanceProperty")
+        if self.distance_property is not None and (not isinstance(self.distance_property, str)
+                                                   or not self.distance_property):
+            raise ValueError("distanceProperty must name an edge property")
+        self.edge_direction = conf.get("edgeDirection", "both")
+        if self.edge_direction not in self.EDGE_DIRECTIONS:
+            raise ValueError('edgeDirection must be "out", "in" or "both"')
 
     class Builder(_Builder):
         def __init__(self):
@@ -174,6 +189,19 @@ class ShortestPathVertexProgram(VertexProgram):
 
         def maxDistance(self, d):  # noqa: N802
             self.configuration["maxDistance"] = int(d)
+            return self
+
+        def distanceProperty(self, key):  # noqa: N802
+            if not isinstance(key, str) or not key:
+                raise ValueError("distanceProperty must name an edge property")
+            self.configuration["distanceProperty"] = key
+            return self
+
+        def edgeDirection(self, d):  # noqa: N802
+            d = d.lower() if isinstance(d, str) else d
+            if d not in ShortestPathVertexProgram.EDGE_DIRECTIONS:
+                raise ValueError('edgeDirection must be "out", "in" or "both"')
+            self.configuration["edgeDirection"] = d
             return self
 
     @classmethod

@@ -307,6 +307,44 @@ JNIEXPORT jint JNICALL FN(peerPressure)(JNIEnv* env, jclass c, jlong g, jint dir
     return st;
 }
 
+JNIEXPORT jint JNICALL FN(ssspKeep)(JNIEnv* env, jclass c, jlong g, jlong source_vid, jint direction) {
+    (void)env;
+    (void)c;
+    return jg_sssp_keep((jg_graph*)(intptr_t)g, source_vid, direction);
+}
+
+JNIEXPORT jint JNICALL FN(ssspKeptRow)(JNIEnv* env, jclass c, jlong g, jobject dist_out) {
+    (void)c;
+    return jg_sssp_kept_row((jg_graph*)(intptr_t)g, (int64_t*)buf(env, dist_out));
+}
+
+JNIEXPORT jint JNICALL FN(ssspKeptRelease)(JNIEnv* env, jclass c, jlong g) {
+    (void)env;
+    (void)c;
+    return jg_sssp_kept_release((jg_graph*)(intptr_t)g);
+}
+
+JNIEXPORT jint JNICALL FN(ssspKeptDag)(JNIEnv* env, jclass c, jlong g, jobject target, jlong max_distance,
+                                       jlongArray out3) {
+    (void)c;
+    int64_t nv = 0, ne = 0, farthest = -1;
+    int st = jg_sssp_kept_dag((jg_graph*)(intptr_t)g, (const uint8_t*)buf(env, target), max_distance, &nv, &ne,
+                              &farthest);
+    if (st == JG_OK) {
+        jlong v[3] = {nv, ne, farthest};
+        (*env)->SetLongArrayRegion(env, out3, 0, 3, v);
+    }
+    return st;
+}
+
+JNIEXPORT jint JNICALL FN(ssspKeptDagRead)(JNIEnv* env, jclass c, jlong g, jlong first, jlong count,
+                                           jobject vertex_out, jobject dist_out, jobject off_out, jobject pred_out) {
+    (void)c;
+    return jg_sssp_kept_dag_read((jg_graph*)(intptr_t)g, first, count, (int32_t*)buf(env, vertex_out),
+                                 (int64_t*)buf(env, dist_out), (int64_t*)buf(env, off_out),
+                                 (int32_t*)buf(env, pred_out));
+}
+
 JNIEXPORT jint JNICALL FN(pagerankTop)(JNIEnv* env, jclass c, jlong g, jlong k, jlongArray listed_out,
                                        jdoubleArray select_ms_out) {
     (void)c;

@@ -123,6 +123,21 @@ final class JanusGpu {
      *  memory.getIteration().  Ties go to the numerically smallest cluster id. */
     static native int peerPressure(long graph, int direction, int distributeVote, int maxIterations,
                                    ByteBuffer clusterVidOut, int[] iterationsOut);
+    /** jg_sssp_keep: the smallest summed edge weights from sourceVid along direction (1 out, 2 in, 3 both; weights
+     *  >= 1, one shard), kept on the device for ssspKeptRow / ssspKeptDag. */
+    static native int ssspKeep(long graph, long sourceVid, int direction);
+    /** jg_sssp_kept_row: the kept distances into an int64 direct buffer of n (Long.MIN_VALUE: unreached). */
+    static native int ssspKeptRow(long graph, ByteBuffer distOut);
+    /** jg_sssp_kept_release: drops the kept distances and their DAG. */
+    static native int ssspKeptRelease(long graph);
+    /** jg_sssp_kept_dag: the minimum-weight-path predecessor DAG of the kept distances, built on the device;
+     *  target: one byte per vertex (null: every reached vertex), maxDistance < 0: no bound;
+     *  out3 = {vertices, predecessor entries, farthest target distance}. */
+    static native int ssspKeptDag(long graph, ByteBuffer target, long maxDistance, long[] out3);
+    /** jg_sssp_kept_dag_read: DAG vertices [first, first + count) into direct buffers (each nullable): int32
+     *  vertices, int64 distances, int64 absolute offsets (count + 1), int32 predecessors. */
+    static native int ssspKeptDagRead(long graph, long first, long count, ByteBuffer vertexOut, ByteBuffer distOut,
+                                      ByteBuffer offOut, ByteBuffer predOut);
     /** jg_pagerank_top: the min(k, n) highest-ranked vertices of the held PageRank session, selected on the
      *  device (rank descending, ties by snapshot order); listedOut[0] = the records listed, selectMsOut[0] =
      *  the select's device time.  The list stays with the graph for pagerankTopRead. */
