@@ -44,6 +44,9 @@
  *   jg_sssp_keep / jg_sssp_kept_dag
  *       TinkerPop ShortestPathVertexProgram with distanceProperty(key) and edgeDirection(dir) [TP-recall]:
  *       summed edge weights along the direction's edges, and the minimum-weight paths' predecessor DAG
+ *   JG_ADJ_EDGE_INDEX / jg_bfs_kept_dag_edges / jg_sssp_kept_dag_edges
+ *       the same program with includeEdges(true) [TP-recall]: a path is v, e, v, ..., v, so the snapshot numbers
+ *       its edges and the DAGs list one entry per edge, parallel edges apart
  *   jg_combine_steps
  *       the same loop for sum/min/max MessageCombiner programs (OLAPTest.DegreeCounter,
  *       janusgraph-test/.../olap/OLAPTest.java:424-503; VertexState.java:85-114)
@@ -75,7 +78,8 @@ extern "C" {
  * jg_builder_finish_labels added; jg_bfs_kept_dag, jg_bfs_kept_dag_read added; jg_cc_census, jg_cc_census_read,
  * jg_cc_census_release added; jg_pagerank_top, jg_pagerank_top_read, jg_pagerank_top_release added;
  * jg_peer_pressure added; JG_ADJ_WEIGHT_BOTH, jg_sssp_keep, jg_sssp_kept_row, jg_sssp_kept_release,
- * jg_sssp_kept_dag, jg_sssp_kept_dag_read added. */
+ * jg_sssp_kept_dag, jg_sssp_kept_dag_read added; JG_ADJ_EDGE_INDEX, jg_graph_neighbor_edges,
+ * jg_bfs_kept_dag_edges, jg_bfs_kept_dag_read_edges, jg_sssp_kept_dag_edges, jg_sssp_kept_dag_read_edges added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -95,6 +99,18 @@ extern "C" {
  * else is JG_ERR_ARG): the BOTH adjacency carries each edge's weight on both of its entries (jg_sssp_keep
  * with JG_DIR_BOTH relaxes it).  Without the flag a build is what it was before the flag existed. */
 #define JG_ADJ_WEIGHT_BOTH 8u
+/* Every adjacency the build makes keeps a uint32 edge ordinal beside each entry: the position of the entry's
+ * edge in the caller's edge list (jg_graph_build: the index into src/dst[0, m); a builder fed ids: the position
+ * in the concatenation of its jg_builder_add_edges / jg_builder_add_labeled_edges chunks, in call order).
+ * Ghost edges and self-loops keep their positions: ordinals count what the caller gave, not what survived.  On
+ * BOTH both entries of an edge carry its ordinal (a self-loop: two entries of one row).  Inside a run of equal
+ * neighbours of a row, ordinals ascend.  Read back by jg_graph_neighbor_edges and listed by the edge-listing
+ * predecessor DAGs (jg_bfs_kept_dag_edges, jg_sssp_kept_dag_edges).
+ * JG_ERR_UNSUPPORTED with the flag: graphs of several shards (logical shards, rank mode); jg_builder_add_rows
+ * builders and jg_graph_build_edgestore (the relation ids the decoder computes are not kept);
+ * jg_builder_finish_labels (its select compacts the list); jg_graph_build_rmat (no caller edge list).
+ * Without the flag a build is what it was before the flag existed: no allocation, no sort payload, no launch. */
+#define JG_ADJ_EDGE_INDEX 16u
 
 /* ---- traversal direction (the MessageScope.Local incident traversal) ---- */
 #define JG_DIR_OUT  1   /* follow u->v edges from u          */
@@ -437,6 +453,20 @@ int jg_bfs_kept_dag(jg_graph* g, int32_t s, const uint8_t* target, int64_t* num_
  * JG_ERR_ARG. */
 int jg_bfs_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
                          int64_t* off_out, int32_t* pred_out);
+/* The edge-listing predecessor DAG of kept row s (ShortestPathVertexProgram's includeEdges: a path is
+ * v, e, v, ..., v and two parallel edges give two paths).  Arguments, preconditions, the backward sweep, the DAG's
+ * vertices, their order and depths, deepest and the stats are jg_bfs_kept_dag's on the same inputs.  The entries
+ * differ: those of v at depth d are one per entry (u, e) of v's row in the reverse adjacency with
+ * depth[u] == d - 1, in row order (the order jg_graph_neighbors / jg_graph_neighbor_edges return them): parallel
+ * edges each get their own entry, a self-loop never qualifies.  num_entries_out counts them.
+ * The DAG occupies jg_bfs_kept_dag's slot: either call replaces what the other held.  jg_bfs_kept_dag_read works
+ * on both kinds (here pred_out repeats u once per parallel edge); jg_bfs_kept_dag_read_edges returns
+ * edge_out = the edge ordinals of entries [off[first], off[first + count]), parallel to pred_out.  On a plain
+ * DAG or with none held: JG_ERR_STATE; a range outside [0, num_vertices]: JG_ERR_ARG.  A graph built without
+ * JG_ADJ_EDGE_INDEX: JG_ERR_UNSUPPORTED from both calls. */
+int jg_bfs_kept_dag_edges(jg_graph* g, int32_t s, const uint8_t* target, int64_t* num_vertices_out,
+                          int64_t* num_entries_out, int32_t* deepest_out);
+int jg_bfs_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint32_t* edge_out);
 
 /* Weighted single-source shortest distances whose distance plane stays on the device (ShortestPathVertexProgram
  * with a distanceProperty): dist[v] = the smallest summed weight of a path source -> v whose edges are followed
@@ -485,6 +515,14 @@ int jg_sssp_kept_dag(jg_graph* g, const uint8_t* target, int64_t max_distance /*
  * held: JG_ERR_STATE; a range outside [0, num_vertices]: JG_ERR_ARG. */
 int jg_sssp_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
                           int64_t* off_out, int32_t* pred_out);
+/* The edge-listing twin of jg_sssp_kept_dag, as jg_bfs_kept_dag_edges is of jg_bfs_kept_dag: the entries of v
+ * are one per entry (u, e) of its reverse row with dist[u] present and dist[u] + w(e) == dist[v], in row order
+ * (of parallel edges every lightest one; a heavier one is not tight).  It occupies jg_sssp_kept_dag's slot;
+ * jg_sssp_kept_dag_read works on both kinds, jg_sssp_kept_dag_read_edges returns the ordinals.  Errors as for
+ * the jg_bfs_kept_dag_edges pair. */
+int jg_sssp_kept_dag_edges(jg_graph* g, const uint8_t* target, int64_t max_distance /* < 0: none */,
+                           int64_t* num_vertices_out, int64_t* num_entries_out, int64_t* farthest_out);
+int jg_sssp_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint32_t* edge_out);
 
 /* Adjacency of vertices rows[0, nrows) (output-order indices), in output-order indices: the host copy
  * of the snapshot a path walk-back reads where Fulgora re-reads each vertex's preloaded BOTH slice
@@ -495,6 +533,11 @@ int jg_sssp_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* ve
  * (nbr_out must be NULL, else JG_ERR_UNSUPPORTED), and rows of other ranks count 0 entries. */
 int jg_graph_neighbors(const jg_graph* g, int32_t direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                        int64_t* nbr_out);
+/* The edge ordinals (JG_ADJ_EDGE_INDEX) of the same entries: same rows, same off_out, same size-first-then-fill
+ * rule; edge_out[i] is the ordinal of the entry whose neighbour jg_graph_neighbors reports at i.  A graph built
+ * without the flag: JG_ERR_UNSUPPORTED. */
+int jg_graph_neighbor_edges(const jg_graph* g, int32_t direction, const int64_t* rows, int64_t nrows,
+                            int64_t* off_out, uint32_t* edge_out);
 
 /* ConnectedComponentVertexProgram: component_vid_out[v] = the vertex id whose decimal String is the
  * component label (the String-minimum id of v's weakly connected component).  iterations_out

@@ -25,6 +25,9 @@ JG_ERR_STATE = -6
 
 ADJ_OUT, ADJ_IN, ADJ_BOTH = 1, 2, 4
 ADJ_WEIGHT_BOTH = 8  # with ADJ_BOTH and weights: the BOTH rows carry each edge's weight (sssp_keep over DIR_BOTH)
+# every adjacency keeps each entry's edge ordinal, its edge's position in the caller's edge list (neighbor_edges,
+# the edge-listing DAGs); one shard, edges given as ids
+ADJ_EDGE_INDEX = 16
 DIR_OUT, DIR_IN, DIR_BOTH = 1, 2, 3
 COMBINE_SUM, COMBINE_MIN, COMBINE_MAX = 0, 1, 2
 FULGORA_HARD_QUERY_LIMIT = 100000
@@ -50,6 +53,8 @@ EXPORTS = [
     "jg_pagerank_top", "jg_pagerank_top_read", "jg_pagerank_top_release",
     "jg_peer_pressure",
     "jg_sssp_keep", "jg_sssp_kept_row", "jg_sssp_kept_release", "jg_sssp_kept_dag", "jg_sssp_kept_dag_read",
+    "jg_graph_neighbor_edges", "jg_bfs_kept_dag_edges", "jg_bfs_kept_dag_read_edges", "jg_sssp_kept_dag_edges",
+    "jg_sssp_kept_dag_read_edges",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -216,6 +221,11 @@ def load():
         "jg_sssp_kept_release": ([_P], ctypes.c_int),
         "jg_sssp_kept_dag": ([_P, _P, _i64, _P, _P, _P], ctypes.c_int),
         "jg_sssp_kept_dag_read": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
+        "jg_graph_neighbor_edges": ([_P, _i32, _P, _i64, _P, _P], ctypes.c_int),
+        "jg_bfs_kept_dag_edges": ([_P, _i32, _P, _P, _P, _P], ctypes.c_int),
+        "jg_bfs_kept_dag_read_edges": ([_P, _i64, _i64, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_edges": ([_P, _P, _i64, _P, _P, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_read_edges": ([_P, _i64, _i64, _P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -668,6 +678,81 @@ class Graph:
             first = last
         return vertex, depth, off, pred
 
+    def _dag_edge_ranges(self, read, read_edges, nv, ne):
+        """(vertex, value, off, pred, edge) of a held edge-listing DAG, its entries read in vertex ranges of at
+        most DAG_READ_ENTRIES (a vertex with more is read alone); read / read_edges: the family's readers."""
+        vertex, value, off, _ = read(0, nv, want_pred=False)
+        pred = np.empty(ne, np.int32)
+        edge = np.empty(ne, np.uint32)
+        first = 0
+        while first < nv:
+            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
+            last = min(max(last, first + 1), nv)
+            b, e = int(off[first]), int(off[last])
+            pred[b:e] = read(first, last - first)[3]
+            edge[b:e] = read_edges(first, last - first, e - b)
+            first = last
+        return vertex, value, off, pred, edge
+
+    def bfs_kept_dag_edges_build(self, s, target=None):
+        """jg_bfs_kept_dag_edges: as bfs_kept_dag_build, for the edge-listing DAG (one entry per qualifying
+        adjacency entry; the graph needs ADJ_EDGE_INDEX).  It replaces a held bfs_kept_dag DAG."""
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, np.uint8)
+            if t.ndim != 1 or len(t) != self.n:
+                raise ValueError("target needs one flag per vertex")
+        nv, ne, deepest = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        check(load().jg_bfs_kept_dag_edges(self._h, int(s), _ptr(t), ctypes.byref(nv), ctypes.byref(ne),
+                                           ctypes.byref(deepest)))
+        return nv.value, ne.value, deepest.value
+
+    def bfs_kept_dag_read_edges(self, first, count, entries=None):
+        """jg_bfs_kept_dag_read_edges: the edge ordinals of the held edge-listing DAG's entries
+        [off[first], off[first + count]) (`entries`: their number, when the caller knows it)."""
+        if entries is None:
+            off = np.empty(count + 1, np.int64)
+            check(load().jg_bfs_kept_dag_read(self._h, int(first), int(count), None, None, _ptr(off), None))
+            entries = int(off[-1] - off[0])
+        edge = np.empty(max(entries, 1), np.uint32)
+        check(load().jg_bfs_kept_dag_read_edges(self._h, int(first), int(count), _ptr(edge)))
+        return edge[:entries]
+
+    def bfs_kept_dag_edges(self, s, target=None):
+        """The edge-listing predecessor DAG of kept row s: (vertex, depth, off, pred, edge).  vertex, depth and
+        their order are bfs_kept_dag's; pred[off[j]:off[j + 1]] lists one predecessor per qualifying entry of
+        vertex[j]'s reverse row, in row order (parallel edges repeat it), edge[...] that entry's edge ordinal."""
+        nv, ne, _ = self.bfs_kept_dag_edges_build(s, target)
+        return self._dag_edge_ranges(self.bfs_kept_dag_read, self.bfs_kept_dag_read_edges, nv, ne)
+
+    def sssp_kept_dag_edges_build(self, target=None, max_distance=-1):
+        """jg_sssp_kept_dag_edges: as sssp_kept_dag_build, for the edge-listing DAG (one entry per tight
+        adjacency entry; the graph needs ADJ_EDGE_INDEX).  It replaces a held sssp_kept_dag DAG."""
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, np.uint8)
+            if t.ndim != 1 or len(t) != self.n:
+                raise ValueError("target needs one flag per vertex")
+        nv, ne, far = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        check(load().jg_sssp_kept_dag_edges(self._h, _ptr(t), int(max_distance), ctypes.byref(nv), ctypes.byref(ne),
+                                            ctypes.byref(far)))
+        return nv.value, ne.value, far.value
+
+    def sssp_kept_dag_read_edges(self, first, count, entries=None):
+        """jg_sssp_kept_dag_read_edges, as bfs_kept_dag_read_edges."""
+        if entries is None:
+            off = np.empty(count + 1, np.int64)
+            check(load().jg_sssp_kept_dag_read(self._h, int(first), int(count), None, None, _ptr(off), None))
+            entries = int(off[-1] - off[0])
+        edge = np.empty(max(entries, 1), np.uint32)
+        check(load().jg_sssp_kept_dag_read_edges(self._h, int(first), int(count), _ptr(edge)))
+        return edge[:entries]
+
+    def sssp_kept_dag_edges(self, target=None, max_distance=-1):
+        """The edge-listing twin of sssp_kept_dag: (vertex, dist, off, pred, edge), as bfs_kept_dag_edges."""
+        nv, ne, _ = self.sssp_kept_dag_edges_build(target, max_distance)
+        return self._dag_edge_ranges(self.sssp_kept_dag_read, self.sssp_kept_dag_read_edges, nv, ne)
+
     def sssp_keep(self, source, direction=DIR_BOTH):
         """jg_sssp_keep: the smallest summed weights from `source` along `direction` (weights >= 1; DIR_BOTH
         needs ADJ_BOTH | ADJ_WEIGHT_BOTH), kept on the device for sssp_kept_row and sssp_kept_dag."""
@@ -741,6 +826,16 @@ class Graph:
         nbr = np.empty(max(int(off[-1]), 1), np.int64)
         check(load().jg_graph_neighbors(self._h, int(direction), _ptr(r), len(r), _ptr(off), _ptr(nbr)))
         return off, nbr[:int(off[-1])]
+
+    def neighbor_edges(self, rows, direction=DIR_BOTH):
+        """jg_graph_neighbor_edges: (off, edge), the edge ordinals of the entries `neighbors` reports, entry
+        for entry (the graph needs ADJ_EDGE_INDEX)."""
+        r = np.ascontiguousarray(np.atleast_1d(rows), np.int64)
+        off = np.empty(len(r) + 1, np.int64)
+        check(load().jg_graph_neighbor_edges(self._h, int(direction), _ptr(r), len(r), _ptr(off), None))
+        edge = np.empty(max(int(off[-1]), 1), np.uint32)
+        check(load().jg_graph_neighbor_edges(self._h, int(direction), _ptr(r), len(r), _ptr(off), _ptr(edge)))
+        return off, edge[:int(off[-1])]
 
     def degrees(self, direction=DIR_BOTH, rows=None):
         """Entries per row of the `direction` adjacency (jg_graph_neighbors' offsets only), all rows by default."""

@@ -325,7 +325,11 @@ class GpuGraphComputer:
 
         edgeDirection("out" | "in") follows the edges one way: the same two routes with that direction, the
         predecessors read from the reverse adjacency (ADJ_IN | ADJ_OUT is built instead of ADJ_BOTH).
-        distanceProperty(key) goes to _weighted_shortest_paths."""
+        distanceProperty(key) goes to _weighted_shortest_paths.
+
+        includeEdges(True): the graph is built with ADJ_EDGE_INDEX and the device route takes the edge-listing
+        DAG (jg_bfs_kept_dag_edges); a path is [vid, Edge, vid, ..., vid], each Edge the object
+        graph.edges[ordinal] (snapshot() lists the edges in that order).  One shard only."""
         if vp.distance_property is not None:
             return self._weighted_shortest_paths(ctx, vp)
         direction = _PATH_DIRECTIONS[vp.edge_direction]
@@ -338,7 +342,18 @@ class GpuGraphComputer:
             target = np.zeros(len(vid), bool)
             target[[index[t] for t in vp.targets if t in index]] = True
         both = direction == _lib.DIR_BOTH
-        g = ctx.build(vid, src, dst, flags=_lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT)
+        flags = _lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT
+        if vp.include_edges:
+            flags |= _lib.ADJ_EDGE_INDEX
+        try:
+            g = ctx.build(vid, src, dst, flags=flags)
+        except _lib.JanusGpuError as e:
+            if vp.include_edges and e.code == _lib.JG_ERR_UNSUPPORTED:
+                # ordinals are kept on one shard only (JG_ADJ_EDGE_INDEX): the Java side keeps delegating
+                raise ProgramNotSupported("ShortestPathVertexProgram with includeEdges is not run on a sharded "
+                                          "graph; delegate to FulgoraGraphComputer") from e
+            raise
+        edges = self.graph.edges
         paths, max_level = [], 0
         max_depth = -1 if vp.max_distance is None else vp.max_distance
         try:
@@ -347,6 +362,14 @@ class GpuGraphComputer:
             dag = DevicePathDag(len(vid)) if on_device else PathDag(neighbors, len(vid))
             for b0 in range(0, len(sources), SOURCES_PER_BFS):
                 batch = sources[b0:b0 + SOURCES_PER_BFS]
+                if vp.include_edges:
+                    g.bfs_keep(vid[batch], direction, max_depth)
+                    for j, s in enumerate(batch):
+                        got, deepest = dag.edge_paths(g.bfs_kept_dag_edges(j, target), s, target)
+                        max_level = max(max_level, deepest)
+                        # even positions hold vertex indices, odd ones edge ordinals
+                        paths.extend([edges[x] if i & 1 else int(vid[x]) for i, x in enumerate(p)] for p in got)
+                    continue
                 if on_device:
                     g.bfs_keep(vid[batch], direction, max_depth)
                     results = (dag.paths(g.bfs_kept_dag(j, target), s, target) for j, s in enumerate(batch))
@@ -510,4 +533,29 @@ class DevicePathDag:
                 j = pos[v]
                 for u in reversed(pred[off[j]:off[j + 1]].tolist()):
                     stack.append((u, suffix + [u]))
+        return out, int(depth[0])
+
+    def edge_paths(self, dag, s, target=None):
+        """`paths` over an edge-listing DAG (Graph.bfs_kept_dag_edges): dag = (vertex, depth, off, pred, edge),
+        each path as alternating vertex index and edge ordinal [v, e, v, ..., v] ([s] from s to itself):
+        targets ascending, first entry first."""
+        vertex, depth, off, pred, edge = dag
+        if len(vertex) == 0:
+            return [], 0
+        pos = np.full(self.n, -1, np.int64)
+        pos[vertex] = np.arange(len(vertex))
+        targets = np.sort(vertex if target is None else vertex[np.asarray(target, bool)[vertex]])
+        off = np.asarray(off).tolist()
+        out = []
+        for t in targets.tolist():
+            stack = [(t, [t])]
+            while stack:
+                v, suffix = stack.pop()
+                if v == s:
+                    out.append(list(reversed(suffix)))
+                    continue
+                j = pos[v]
+                b, e = off[j], off[j + 1]
+                for u, x in zip(reversed(pred[b:e].tolist()), reversed(edge[b:e].tolist())):
+                    stack.append((u, suffix + [x, u]))
         return out, int(depth[0])

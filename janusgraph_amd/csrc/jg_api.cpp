@@ -924,6 +924,14 @@ static bool weight_both_ok(uint32_t flags, bool has_weights) {
 }
 static const char* const kWeightBothRule = "JG_ADJ_WEIGHT_BOTH needs JG_ADJ_BOTH and edge weights";
 
+// JG_ADJ_EDGE_INDEX: an ordinal is a position in the edge list the caller gave, so a build that holds no such
+// list (`no_list`: why, or null) and graphs of several shards refuse the flag
+static void edge_index_check(uint32_t flags, const jg::Ctx& c, const char* no_list) {
+    if (!(flags & JG_ADJ_EDGE_INDEX)) return;
+    if (no_list) jg::fail(JG_ERR_UNSUPPORTED, std::string("JG_ADJ_EDGE_INDEX: ") + no_list);
+    if (c.total_shards() != 1) jg::fail(JG_ERR_UNSUPPORTED, "JG_ADJ_EDGE_INDEX: graphs of one shard only");
+}
+
 int jg_graph_build(jg_ctx* ctx, const int64_t* vid, int64_t n, const int64_t* src, const int64_t* dst,
                    const int32_t* weight, int64_t m, uint32_t flags, jg_graph** out) {
     JG_GUARD_BEGIN
@@ -933,10 +941,11 @@ int jg_graph_build(jg_ctx* ctx, const int64_t* vid, int64_t n, const int64_t* sr
     JG_ARG(m == 0 || (src && dst), "src/dst is null");
     JG_ARG(n < (int64_t)INT32_MAX, "more than 2^31-1 vertices");
     JG_ARG(m < (int64_t)UINT32_MAX, "more than 2^32-1 edges");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~31u) == 0, "bad adjacency flags");
     JG_ARG(weight_both_ok(flags, weight != nullptr), kWeightBothRule);
     *out = nullptr;
     jg::Ctx& c = ctx->impl;
+    edge_index_check(flags, c, nullptr);
     auto gh = std::make_unique<jg_graph>(&c);
     jg::Graph& g = gh->impl;
     g.flags = flags;
@@ -973,8 +982,9 @@ int jg_graph_build_edgestore(jg_ctx* ctx, const uint64_t* row_keys, int64_t nrow
                              jg_graph** out) {
     JG_GUARD_BEGIN
     JG_ARG(ctx && out, "null argument");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~31u) == 0, "bad adjacency flags");
     JG_ARG(weight_both_ok(flags, false), kWeightBothRule);
+    edge_index_check(flags, ctx->impl, "edgestore rows keep no relation ids to number their edges by");
     const jg::EdgestoreRows r{row_keys, nrows,     row_entry_off, bytes,    nbytes,        entry_off,
                               value_pos, nentries, type_ids,      type_mult, ntypes,       partition_bits};
     *out = nullptr;  // the decoder validates the rows and entries as it stages them
@@ -1180,11 +1190,12 @@ int jg_builder_add_rows(jg_builder* b, const uint64_t* row_keys, int64_t nrows, 
 int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
     JG_GUARD_BEGIN
     JG_ARG(b && out, "null argument");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~31u) == 0, "bad adjacency flags");
     JG_ARG(weight_both_ok(flags, b->mode == 2 ? (b->dec && b->dec->weighted == 1) : b->weights == 1), kWeightBothRule);
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     *out = nullptr;
     jg::Ctx& c = *b->ctx;
+    edge_index_check(flags, c, b->mode == 2 ? "edgestore rows keep no relation ids to number their edges by" : nullptr);
     auto gh = std::make_unique<jg_graph>(&c);
     jg::Graph& g = gh->impl;
     g.flags = flags;
@@ -1246,10 +1257,11 @@ int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
 int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabels, uint32_t flags, jg_graph** out) {
     JG_GUARD_BEGIN
     JG_ARG(b && out, "null argument");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~31u) == 0, "bad adjacency flags");
     JG_ARG(weight_both_ok(flags, b->mode == 2 ? (b->dec && b->dec->weighted == 1) : b->weights == 1), kWeightBothRule);
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     if (!b->keep_labels) jg::fail(JG_ERR_STATE, "jg_builder_finish_labels needs jg_builder_keep_labels before the first chunk");
+    edge_index_check(flags, *b->ctx, "a label scope's select compacts the edge list");
     static_assert(JG_MAX_SCOPE_LABELS == jg::kScopeMaxLabels, "the header's cap is the select's");
     std::vector<int64_t> set;
     switch (jg::label_set_prepare(labels, nlabels, set)) {
@@ -1325,8 +1337,9 @@ int jg_graph_build_rmat(jg_ctx* ctx, int scale, int edgefactor, uint64_t seed, u
     JG_GUARD_BEGIN
     JG_ARG(ctx && out, "null argument");
     JG_ARG(scale >= 1 && scale <= 30 && edgefactor >= 1 && edgefactor <= 64, "bad RMAT scale/edgefactor");
-    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~15u) == 0, "bad adjacency flags");
+    JG_ARG((flags & (JG_ADJ_IN | JG_ADJ_OUT | JG_ADJ_BOTH)) != 0 && (flags & ~31u) == 0, "bad adjacency flags");
     JG_ARG(weight_both_ok(flags, false), kWeightBothRule);
+    edge_index_check(flags, ctx->impl, "a generated graph has no caller edge list");
     *out = nullptr;
     const int64_t n = 1ll << scale, m = (int64_t)edgefactor << scale;
     JG_ARG(m < (int64_t)UINT32_MAX, "too many edges");
@@ -1588,6 +1601,21 @@ int jg_bfs_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* ver
     JG_GUARD_END
 }
 
+int jg_bfs_kept_dag_edges(jg_graph* g, int32_t s, const uint8_t* target, int64_t* num_vertices_out,
+                          int64_t* num_entries_out, int32_t* deepest_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::bfs_kept_dag(g->impl, s, target, num_vertices_out, num_entries_out, deepest_out, true);
+    JG_GUARD_END
+}
+
+int jg_bfs_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint32_t* edge_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::bfs_kept_dag_read_edges(g->impl, first, count, edge_out);
+    JG_GUARD_END
+}
+
 int jg_sssp_keep(jg_graph* g, int64_t source_vid, int32_t direction) {
     JG_GUARD_BEGIN
     JG_ARG(g, "null graph");
@@ -1625,11 +1653,34 @@ int jg_sssp_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* ve
     JG_GUARD_END
 }
 
+int jg_sssp_kept_dag_edges(jg_graph* g, const uint8_t* target, int64_t max_distance, int64_t* num_vertices_out,
+                           int64_t* num_entries_out, int64_t* farthest_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag(g->impl, target, max_distance, num_vertices_out, num_entries_out, farthest_out, true);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint32_t* edge_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag_read_edges(g->impl, first, count, edge_out);
+    JG_GUARD_END
+}
+
 int jg_graph_neighbors(const jg_graph* g, int32_t direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                        int64_t* nbr_out) {
     JG_GUARD_BEGIN
     JG_ARG(g, "null graph");
     jg::graph_neighbors(g->impl, direction, rows, nrows, off_out, nbr_out);
+    JG_GUARD_END
+}
+
+int jg_graph_neighbor_edges(const jg_graph* g, int32_t direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
+                            uint32_t* edge_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::graph_neighbor_edges(g->impl, direction, rows, nrows, off_out, edge_out);
     JG_GUARD_END
 }
 

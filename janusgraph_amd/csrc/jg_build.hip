@@ -577,13 +577,16 @@ void dense_of_vids(const Graph& g, const int64_t* vids, int64_t k, int64_t* out,
     if (padded) copy_d2h(padded, pr.get(), (size_t)k * sizeof(int64_t), s);
 }
 
-static void build_csr(Shard& sh, const SelectArgs& a, const int32_t* weight, Csr& csr, hipStream_t s) {
+// keep_eidx (JG_ADJ_EDGE_INDEX): the sorted ordinals stay with the CSR (Csr::eidx).  The sort is LSD, so stable,
+// and the select emits entries in edge order: inside a run of equal (row, column) keys ordinals ascend.
+static void build_csr(Shard& sh, const SelectArgs& a, const int32_t* weight, bool keep_eidx, Csr& csr, hipStream_t s) {
     DevBuf<uint64_t> keys;
     DevBuf<uint32_t> eidx;
-    const int64_t nnz = select_keys(a, keys, eidx, weight != nullptr, s);
+    const bool payload = weight != nullptr || keep_eidx;
+    const int64_t nnz = select_keys(a, keys, eidx, payload, s);
     const int rbits = bits_for((uint64_t)std::max<int64_t>(sh.rows - 1, 0));
     if (rbits + a.cbits > 64) fail(JG_ERR_UNSUPPORTED, "CSR sort key exceeds 64 bits");
-    prim::radix_sort(keys.get(), weight ? eidx.get() : nullptr, nnz, rbits + a.cbits, s);
+    prim::radix_sort(keys.get(), payload ? eidx.get() : nullptr, nnz, rbits + a.cbits, s);
     csr.rows = sh.rows;
     csr.nnz = nnz;
     csr.row_ptr.alloc(sh.rows + 1);
@@ -599,6 +602,7 @@ static void build_csr(Shard& sh, const SelectArgs& a, const int32_t* weight, Csr
         JG_LAUNCH_CHECK();
     }
     JG_HIP(hipStreamSynchronize(s));
+    if (keep_eidx) csr.eidx.swap(eidx);
 }
 
 // ---------------- the sliced split (SliceBand) ----------------
@@ -1127,6 +1131,12 @@ void build_graph_from_dense(Graph& g, DenseEdges& e) {
     const int mode = (g.flags & JG_ADJ_IN) ? 0 : (g.flags & JG_ADJ_BOTH) ? 1 : 2;
     const int vbits = bits_for((uint64_t)std::max<int64_t>(n - 1, 0));
     const int cbits = std::max(1, bits_for((uint64_t)(g.padded_len() - 1)));
+    // JG_ADJ_EDGE_INDEX: ordinals index the one edge list the caller gave, on the one shard that holds every row
+    const bool keep_eidx = (g.flags & JG_ADJ_EDGE_INDEX) != 0;
+    if (keep_eidx && (P != 1 || g.shards.size() != 1))
+        fail(JG_ERR_UNSUPPORTED, "JG_ADJ_EDGE_INDEX: graphs of one shard only");
+    if (keep_eidx && e.capped)
+        fail(JG_ERR_UNSUPPORTED, "JG_ADJ_EDGE_INDEX: not under a query limit (the capped lists are not the caller's)");
     bool first = true;
     for (size_t li = 0; li < g.shards.size(); ++li) {
         Shard& sh = *g.shards[li];
@@ -1271,7 +1281,7 @@ void build_graph_from_dense(Graph& g, DenseEdges& e) {
             }
             a.cbits = std::max(cbits, bits_for((uint64_t)(col_space - 1)));  // compact ids may exceed P*S
             // round 3: one column-ordered build, the bands cut from it (band_count / band_scatter)
-            build_csr(sh, a, wt, csr, s);
+            build_csr(sh, a, wt, keep_eidx, csr, s);
             // the gathered vector of the split: PageRank's fp64 contributions (IN); on BOTH the 64-source
             // BFS's uint64 frontier words on one shard (its main user since CC runs a union-find there:
             // RMAT-26 11.0 -> 10.35 ms with 64 band-0 sub-slices instead of 32, CC unchanged; round 5,
@@ -1296,7 +1306,7 @@ void build_graph_from_dense(Graph& g, DenseEdges& e) {
             } else {  // sharded OUT has no halo plan: global columns, class plan built on first use
                 use(outl);
                 a.which = 1;
-                build_csr(sh, a, w, sh.out, s);
+                build_csr(sh, a, w, false, sh.out, s);  // (P > 1: no ordinals)
             }
         }
         // (JG_ADJ_WEIGHT_BOTH: each edge's weight on both of its entries, for jg_sssp_keep over JG_DIR_BOTH)

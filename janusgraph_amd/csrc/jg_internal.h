@@ -36,6 +36,9 @@ struct Csr {
     DevBuf<int64_t> row_ptr;
     DevBuf<int32_t> col;
     DevBuf<int32_t> weight;  // optional (SD weights)
+    // optional (JG_ADJ_EDGE_INDEX): each entry's edge ordinal, its edge's position in the caller's edge list;
+    // inside a run of equal columns ordinals ascend (a stable sort over entries selected in edge order)
+    DevBuf<uint32_t> eidx;
     // rows [empty_from, rows) have no entries (set with the pull plan: 1 + the last non-empty row;
     // -1 when unknown)
     mutable int64_t empty_from = -1;
@@ -47,7 +50,7 @@ struct Csr {
     mutable long long wstat[4] = {0, 0, 0, 0};  // sd_weight_stats: min, sum, count, max
     mutable bool wstat_ok = false;
     bool present() const { return row_ptr.size() > 0; }
-    int64_t bytes() const { return (int64_t)(row_ptr.bytes() + col.bytes() + weight.bytes()); }
+    int64_t bytes() const { return (int64_t)(row_ptr.bytes() + col.bytes() + weight.bytes() + eidx.bytes()); }
 };
 
 // Degree-class plan for the pull kernels of one CSR on one shard.  Rows are sorted by degree
@@ -267,12 +270,14 @@ struct Shard {
     // descending): caller-order vertex and depth, offsets into dag_pred, caller-order predecessors
     DevBuf<int32_t> dag_vertex, dag_depth, dag_pred;
     DevBuf<int64_t> dag_off;                 // [dag_nv + 1]
+    DevBuf<uint32_t> dag_edge;               // an edge-listing DAG's ordinals, parallel to dag_pred (Graph::dag_edges)
     // jg_sssp_keep's distance plane ([rows] int64, local row order, LLONG_MIN: absent) and the tight-edge
     // predecessor DAG of it (jg_sssp_kept_dag; Graph::wdag_nv vertices, distance descending): buffers of
     // their own, so that a kept BFS row and its DAG can be held at the same time
     DevBuf<long long> sssp_dist;
     DevBuf<int32_t> wdag_vertex, wdag_pred;
     DevBuf<int64_t> wdag_dist, wdag_off;     // [wdag_nv], [wdag_nv + 1]
+    DevBuf<uint32_t> wdag_edge;              // as dag_edge (Graph::wdag_edges)
     // the held component census (jg_cc_census, jg_census.hip; Graph::census_listed pairs, population
     // descending): the component's vertex id and its population.  Its own buffers, not program scratch.
     DevBuf<int64_t> census_vid, census_pop;
@@ -321,9 +326,11 @@ struct Graph {
     int kept_nsrc = 0;  // depth rows kept by jg_bfs_keep
     int kept_dir = 0;   // the direction of that traversal (jg_bfs_kept_dag reads the reverse adjacency)
     int64_t dag_nv = -1, dag_ne = 0;  // the held predecessor DAG (Shard::dag_*); -1: none
+    bool dag_edges = false;           // it lists edges (jg_bfs_kept_dag_edges): one entry per qualifying adjacency entry
     bool sssp_kept = false;           // jg_sssp_keep's plane is held (Shard::sssp_dist)
     int sssp_dir = 0;                 // its direction (jg_sssp_kept_dag reads the reverse adjacency)
     int64_t wdag_nv = -1, wdag_ne = 0;  // the held weighted predecessor DAG (Shard::wdag_*); -1: none
+    bool wdag_edges = false;            // it lists edges (jg_sssp_kept_dag_edges)
     int64_t census_listed = -1;       // the held component census (Shard::census_*); -1: none
     // the held PageRank top list (jg_pagerank_top, jg_top.hip; top_listed records in the list's order): the
     // caller-order index, rank and edgeCount of each, merged from the shards' selects and held on the host
@@ -579,15 +586,21 @@ void bfs_run(Graph& g, const int64_t* source_vids, int nsrc, int direction, int 
 void bfs_kept_row(Graph& g, int s, int32_t* depth_out);  // row s in caller order
 void bfs_kept_release(Graph& g);
 // jg_bfs_kept_dag / jg_bfs_kept_dag_read (jg_pathdag.hip): the predecessor DAG of kept row s, one shard
-void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out, int32_t* deepest_out);
+// (edges: jg_bfs_kept_dag_edges, one entry per qualifying adjacency entry and its edge ordinal beside it)
+void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out, int32_t* deepest_out,
+                  bool edges = false);
 void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
                        int64_t* off_out, int32_t* pred_out);
+void bfs_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out);
 void bfs_kept_dag_drop(Graph& g);
 // Zeroes the occupied positions of a shard's gathered vector of adjacency `adj` (own rows + peer runs).
 void zero_gathered(const Graph& g, const Shard& sh, uint32_t adj, void* v, size_t eb);
 // jg_graph_neighbors: the adjacency `direction` of caller vertices rows[0, nrows) in caller order
 void graph_neighbors(const Graph& g, int direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                      int64_t* nbr_out);
+// jg_graph_neighbor_edges: the edge ordinals of the same entries (JG_ADJ_EDGE_INDEX graphs: one shard)
+void graph_neighbor_edges(const Graph& g, int direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
+                          uint32_t* edge_out);
 void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* dist_out);
 // jg_sssp_keep / jg_sssp_kept_row / jg_sssp_kept_release (jg_sssp.hip): one shard; the plane stays in
 // Shard::sssp_dist
@@ -595,10 +608,12 @@ void sssp_keep(Graph& g, int64_t source_vid, int direction);
 void sssp_kept_row(Graph& g, int64_t* dist_out);
 void sssp_kept_release(Graph& g);
 // jg_sssp_kept_dag / jg_sssp_kept_dag_read (jg_pathdag.hip): the tight-edge predecessor DAG of the kept plane
+// (edges: jg_sssp_kept_dag_edges)
 void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
-                   int64_t* farthest_out);
+                   int64_t* farthest_out, bool edges = false);
 void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
                         int64_t* off_out, int32_t* pred_out);
+void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out);
 void sssp_kept_dag_drop(Graph& g);
 // The batches of the device-controlled loops (shortest distance's steps, the weighted DAG's rounds), whose
 // state the host reads once per batch: a first batch (the loop's own estimate), then 8, 16, ... 64 steps

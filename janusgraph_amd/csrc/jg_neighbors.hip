@@ -136,4 +136,41 @@ void graph_neighbors(const Graph& g, int direction, const int64_t* rows, int64_t
     }
 }
 
+// The edge ordinals of the entries graph_neighbors reports, entry for entry: the same rows of the same CSR,
+// gathered from Csr::eidx instead of Csr::col (no id mapping: an ordinal is the caller's already).
+void graph_neighbor_edges(const Graph& g, int direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
+                          uint32_t* edge_out) {
+    if (direction < JG_DIR_OUT || direction > JG_DIR_BOTH) fail(JG_ERR_ARG, "bad direction");
+    if (nrows < 0 || (nrows > 0 && !rows) || !off_out) fail(JG_ERR_ARG, "bad arguments");
+    if (!(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, "jg_graph_neighbor_edges: the graph was built without JG_ADJ_EDGE_INDEX");
+    const uint32_t adj = direction == JG_DIR_BOTH ? JG_ADJ_BOTH : direction == JG_DIR_OUT ? JG_ADJ_OUT : JG_ADJ_IN;
+    if (!(g.flags & adj)) fail(JG_ERR_UNSUPPORTED, "the graph was built without this adjacency");
+    const Shard& sh = *g.shards[0];  // the flag is refused on graphs of several shards
+    const Csr& c = pick(sh, direction);
+    std::vector<int64_t> loc((size_t)nrows);
+    for (int64_t k = 0; k < nrows; ++k) {
+        if (rows[k] < 0 || rows[k] >= g.n) fail(JG_ERR_ARG, "row outside [0, num_vertices)");
+        loc[(size_t)k] = g.padded_of_dense()[(size_t)rows[k]];
+    }
+    off_out[0] = 0;
+    if (nrows == 0) return;
+    DeviceGuard dg(sh);
+    DevBuf<int64_t> drows(nrows), dlen(nrows);
+    copy_h2d(drows.get(), loc.data(), (size_t)nrows * sizeof(int64_t), sh.stream);
+    row_bounds_kernel<<<grid_for(nrows), kBlock, 0, sh.stream>>>(c.row_ptr.get(), drows.get(), nrows, dlen.get());
+    JG_LAUNCH_CHECK();
+    std::vector<int64_t> len((size_t)nrows);
+    copy_d2h(len.data(), dlen.get(), (size_t)nrows * sizeof(int64_t), sh.stream);
+    for (int64_t k = 0; k < nrows; ++k) off_out[k + 1] = off_out[k] + len[(size_t)k];
+    if (!edge_out || off_out[nrows] == 0) return;
+    DevBuf<int64_t> doff(nrows + 1);
+    DevBuf<int32_t> dout(off_out[nrows]);
+    copy_h2d(doff.get(), off_out, (size_t)(nrows + 1) * sizeof(int64_t), sh.stream);
+    gather_rows_kernel<<<(unsigned)std::min<int64_t>(nrows, 65536), kBlock, 0, sh.stream>>>(
+        c.row_ptr.get(), reinterpret_cast<const int32_t*>(c.eidx.get()), drows.get(), doff.get(), nrows, dout.get());
+    JG_LAUNCH_CHECK();
+    copy_d2h(edge_out, dout.get(), (size_t)off_out[nrows] * sizeof(uint32_t), sh.stream);
+}
+
 }  // namespace jg

@@ -26,6 +26,11 @@
 // device") shares the emit: the count and fill passes are templates over the DAG's flavour (HopDag: depth
 // planes and "one level up"; TightDag: distance planes and "a tight edge"), which names the per-vertex value
 // and decides whether an entry counts.  Its sweep runs by rounds instead of levels (wdag_round_kernel).
+//
+// The edge-listing DAGs (jg_bfs_kept_dag_edges, jg_sssp_kept_dag_edges; DESIGN.md, "Edge-listing predecessor
+// DAG") are the same sweeps with two more flavours (HopEdgeDag, TightEdgeDag): the predicate without the
+// de-duplication, so every qualifying entry of a run of parallel edges is listed, and the fill pass stores the
+// entry's edge ordinal (Csr::eidx, JG_ADJ_EDGE_INDEX) beside its predecessor.
 #include <climits>
 
 #include "jg_frontier.h"
@@ -182,14 +187,25 @@ __global__ void dag_unpack_kernel(const uint64_t* __restrict__ key, const uint32
 // adjacency (column x, the k-th of its row) is listed as a predecessor of DAG row i.
 struct HopDag {  // jg_bfs_kept_dag: one level up, the first entry of its equal-column run
     using Val = int32_t;
+    static constexpr bool kEdges = false;
     struct Extra {};
     template <class W>
     static __device__ __forceinline__ bool counts(const W& a, int64_t i, int32_t x, int64_t p, int64_t k) {
         return a.dep[x] == a.depth[i] - 1 && (k == 0 || a.col[p - 1] != x);
     }
 };
+struct HopEdgeDag {  // jg_bfs_kept_dag_edges: one level up, every entry (a self-loop is never one level up)
+    using Val = int32_t;
+    static constexpr bool kEdges = true;
+    struct Extra {};
+    template <class W>
+    static __device__ __forceinline__ bool counts(const W& a, int64_t i, int32_t x, int64_t, int64_t) {
+        return a.dep[x] == a.depth[i] - 1;
+    }
+};
 struct TightDag {  // jg_sssp_kept_dag: a tight edge, the first of its weight in its equal-column run
     using Val = long long;
+    static constexpr bool kEdges = false;
     struct Extra {
         const int32_t* wt;
     };
@@ -204,6 +220,17 @@ struct TightDag {  // jg_sssp_kept_dag: a tight edge, the first of its weight in
         for (int64_t q = p - 1; q >= p - k && a.col[q] == x; --q)
             if (a.wt[q] == w) return false;
         return true;
+    }
+};
+struct TightEdgeDag {  // jg_sssp_kept_dag_edges: every tight entry (weights are positive: a self-loop is never tight)
+    using Val = long long;
+    static constexpr bool kEdges = true;
+    using Extra = TightDag::Extra;
+    template <class W>
+    static __device__ __forceinline__ bool counts(const W& a, int64_t i, int32_t x, int64_t p, int64_t) {
+        const int32_t w = a.wt[p];
+        const long long du = a.dep[x];
+        return w != INT32_MIN && du != LLONG_MIN && du + (long long)w == a.depth[i];
     }
 };
 
@@ -222,6 +249,8 @@ struct DagWalk : T::Extra {
     int32_t *r_fi, *r_li, *r_ca, *r_cl;
     const int64_t* off;     // [nv + 1] exclusive scan of cnt (fill)
     int32_t* pred;          // [off[nv]] (fill)
+    const uint32_t* eidx;   // the adjacency's edge ordinals (edge flavours; else null)
+    uint32_t* edge;         // [off[nv]] each listed entry's ordinal, parallel to pred (edge flavours, fill)
 };
 
 // One step of a range: lane l looks at edge sb + l.  Returns whether the lane's entry counts; i = its DAG
@@ -231,10 +260,11 @@ struct DagLane {
     int32_t i, x;
     uint64_t mask;
     int lo;  // the row's first lane in this step
+    int64_t p;  // the entry's position in the adjacency
 };
 template <class T>
 __device__ __forceinline__ DagLane dag_lane(const DagWalk<T>& a, EdgeCursor& cur, int64_t sb, int64_t end) {
-    DagLane r{false, false, 0, 0, 0ull, 0};
+    DagLane r{false, false, 0, 0, 0ull, 0, 0};
     const int64_t e = sb + lane_id();
     r.valid = e < end;
     if (r.valid) {
@@ -242,6 +272,7 @@ __device__ __forceinline__ DagLane dag_lane(const DagWalk<T>& a, EdgeCursor& cur
         r.i = (int32_t)cur.i;
         const int64_t q0 = a.qoff[cur.i];
         const int64_t p = a.rp[a.local[cur.i]] + (e - q0);
+        r.p = p;
         r.x = a.col[p];
         r.counts = T::counts(a, cur.i, r.x, p, e - q0);
         const int64_t lo = q0 > sb ? q0 - sb : 0;
@@ -308,7 +339,11 @@ __global__ __launch_bounds__(kBlock) void dag_fill_kernel(DagWalk<T> a) {
             const DagLane r = dag_lane(a, cur, sb, end);
             const uint64_t b = __ballot(r.counts);
             const int32_t before = r.valid && r.i == open_row ? open_carry : 0;
-            if (r.counts) a.pred[a.off[r.i] + before + __popcll(b & r.mask & lanemask_lt())] = a.dense[r.x];
+            if (r.counts) {
+                const int64_t slot = a.off[r.i] + before + __popcll(b & r.mask & lanemask_lt());
+                a.pred[slot] = a.dense[r.x];
+                if constexpr (T::kEdges) a.edge[slot] = a.eidx[r.p];
+            }
             // the step's last row stays open
             const int nvalid = end - sb < kWave ? (int)(end - sb) : kWave;
             const int32_t tot = before + __popcll(b & r.mask);
@@ -447,12 +482,20 @@ void bfs_kept_dag_drop(Graph& g) {
         sp->dag_depth.reset();
         sp->dag_pred.reset();
         sp->dag_off.reset();
+        sp->dag_edge.reset();
     }
     g.dag_nv = -1;
     g.dag_ne = 0;
+    g.dag_edges = false;
 }
 
-void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out, int32_t* deepest_out) {
+// T: HopDag (jg_bfs_kept_dag) or HopEdgeDag (jg_bfs_kept_dag_edges).  Seed, sweep and the DAG's vertices do not
+// depend on T; the count and fill passes do.
+template <class T>
+static void bfs_kept_dag_t(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out,
+                           int32_t* deepest_out) {
+    if (T::kEdges && !(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag_edges: the graph was built without JG_ADJ_EDGE_INDEX");
     if (g.P != 1 || g.shards.size() != 1)
         fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag runs on one shard (sharded graphs: walk back on the host)");
     if (s < 0 || s >= g.kept_nsrc) fail(JG_ERR_ARG, "no kept depth row with that index (jg_bfs_keep)");
@@ -473,6 +516,7 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     const auto finish = [&](int64_t nv, int64_t ne, int32_t deepest) {
         g.dag_nv = nv;
         g.dag_ne = ne;
+        g.dag_edges = T::kEdges;
         if (nv_out) *nv_out = nv;
         if (ne_out) *ne_out = ne;
         if (deepest_out) *deepest_out = deepest;
@@ -561,11 +605,12 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
     DevBuf<int32_t> rfi((size_t)std::max<int64_t>(nranges, 1)), rli((size_t)std::max<int64_t>(nranges, 1)),
         rca((size_t)std::max<int64_t>(nranges, 1)), rcl((size_t)std::max<int64_t>(nranges, 1));
-    DagWalk<HopDag> wk{{}, local.get(), sh.dag_depth.get(), qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(), dep,
-                       sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr, nullptr};
+    DagWalk<T> wk{{}, local.get(), sh.dag_depth.get(), qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(), dep,
+                  sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr, nullptr,
+                  T::kEdges ? c.eidx.get() : nullptr, nullptr};
     const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
     if (mf > 0) {
-        dag_count_kernel<HopDag><<<walk_grid, kBlock, 0, st>>>(wk);
+        dag_count_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
         JG_LAUNCH_CHECK();
         ++launches;
     }
@@ -573,10 +618,12 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     int64_t ne = 0;
     copy_d2h(&ne, sh.dag_off.get() + nv, sizeof(int64_t), st);
     sh.dag_pred.alloc((size_t)std::max<int64_t>(ne, 1));
+    if (T::kEdges) sh.dag_edge.alloc((size_t)std::max<int64_t>(ne, 1));
     if (mf > 0) {
         wk.off = sh.dag_off.get();
         wk.pred = sh.dag_pred.get();
-        dag_fill_kernel<HopDag><<<walk_grid, kBlock, 0, st>>>(wk);
+        wk.edge = sh.dag_edge.get();
+        dag_fill_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
         JG_LAUNCH_CHECK();
         ++launches;
     }
@@ -592,8 +639,17 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     // per row per compaction (flag + position).  Each of the three walks (sweep, count, fill) reads a
     // DAG-row entry's column and probes its depth: 3 x 8 B per entry.  A DAG vertex costs ~64 B (two
     // sort records of 12 B read and written, queue entry, row_ptr pair, count, offset, outputs), an
-    // emitted predecessor 8 B (dense probe + store).
-    ctx.last.algorithmic_bytes = 28.0 * (double)rows + 24.0 * (double)mf + 64.0 * (double)nv + 8.0 * (double)ne;
+    // emitted predecessor 8 B (dense probe + store).  The edge-listing DAG adds the ordinal: 4 B per walked
+    // entry in the fill pass (the listed entries' ordinals, fetched by the line) and 4 B per emitted entry (its
+    // store); the count pass reads no ordinal.
+    ctx.last.algorithmic_bytes = 28.0 * (double)rows + 24.0 * (double)mf + 64.0 * (double)nv + 8.0 * (double)ne +
+                                 (T::kEdges ? 4.0 * (double)mf + 4.0 * (double)ne : 0.0);
+}
+
+void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out, int32_t* deepest_out,
+                  bool edges) {
+    if (edges) bfs_kept_dag_t<HopEdgeDag>(g, s, target, nv_out, ne_out, deepest_out);
+    else bfs_kept_dag_t<HopDag>(g, s, target, nv_out, ne_out, deepest_out);
 }
 
 void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
@@ -619,6 +675,22 @@ void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_o
     }
 }
 
+void bfs_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {
+    if (!(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag_read_edges: the graph was built without JG_ADJ_EDGE_INDEX");
+    if (g.dag_nv < 0 || !g.dag_edges) fail(JG_ERR_STATE, "no edge-listing predecessor DAG is held (jg_bfs_kept_dag_edges)");
+    if (first < 0 || count < 0 || first > g.dag_nv || count > g.dag_nv - first)
+        fail(JG_ERR_ARG, "range outside the DAG's vertices");
+    if (g.dag_nv == 0 || count == 0 || !edge_out) return;
+    Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    hipStream_t st = sh.stream;
+    int64_t b = 0, e = 0;
+    copy_d2h(&b, sh.dag_off.get() + first, sizeof(int64_t), st);
+    copy_d2h(&e, sh.dag_off.get() + first + count, sizeof(int64_t), st);
+    copy_d2h(edge_out, sh.dag_edge.get() + b, (size_t)(e - b) * sizeof(uint32_t), st);
+}
+
 void sssp_kept_dag_drop(Graph& g) {
     for (auto& sp : g.shards) {
         DeviceGuard dg(*sp);
@@ -626,13 +698,19 @@ void sssp_kept_dag_drop(Graph& g) {
         sp->wdag_dist.reset();
         sp->wdag_pred.reset();
         sp->wdag_off.reset();
+        sp->wdag_edge.reset();
     }
     g.wdag_nv = -1;
     g.wdag_ne = 0;
+    g.wdag_edges = false;
 }
 
-void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
-                   int64_t* farthest_out) {
+// T: TightDag (jg_sssp_kept_dag) or TightEdgeDag (jg_sssp_kept_dag_edges), as bfs_kept_dag_t
+template <class T>
+static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
+                            int64_t* farthest_out) {
+    if (T::kEdges && !(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag_edges: the graph was built without JG_ADJ_EDGE_INDEX");
     if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag runs on one shard");
     if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep)");
     Shard& sh = *g.shards[0];
@@ -653,6 +731,7 @@ void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_
     const auto finish = [&](int64_t nv, int64_t ne, int64_t farthest, int64_t rounds) {
         g.wdag_nv = nv;
         g.wdag_ne = ne;
+        g.wdag_edges = T::kEdges;
         if (nv_out) *nv_out = nv;
         if (ne_out) *ne_out = ne;
         if (farthest_out) *farthest_out = farthest;
@@ -750,12 +829,12 @@ void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_
     const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
     const size_t nr = (size_t)std::max<int64_t>(nranges, 1);
     DevBuf<int32_t> rfi(nr), rli(nr), rca(nr), rcl(nr);
-    DagWalk<TightDag> wk{{c.weight.get()}, local.get(), wd, qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(),
-                         dist, sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr,
-                         nullptr};
+    DagWalk<T> wk{{c.weight.get()}, local.get(), wd, qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(),
+                  dist, sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr,
+                  nullptr, T::kEdges ? c.eidx.get() : nullptr, nullptr};
     const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
     if (mf > 0) {
-        dag_count_kernel<TightDag><<<walk_grid, kBlock, 0, st>>>(wk);
+        dag_count_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
         JG_LAUNCH_CHECK();
         ++launches;
     }
@@ -763,10 +842,12 @@ void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_
     int64_t ne = 0;
     copy_d2h(&ne, sh.wdag_off.get() + nv, sizeof(int64_t), st);
     sh.wdag_pred.alloc((size_t)std::max<int64_t>(ne, 1));
+    if (T::kEdges) sh.wdag_edge.alloc((size_t)std::max<int64_t>(ne, 1));
     if (mf > 0) {
         wk.off = sh.wdag_off.get();
         wk.pred = sh.wdag_pred.get();
-        dag_fill_kernel<TightDag><<<walk_grid, kBlock, 0, st>>>(wk);
+        wk.edge = sh.wdag_edge.get();
+        dag_fill_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
         JG_LAUNCH_CHECK();
         ++launches;
     }
@@ -784,8 +865,16 @@ void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_
     // its distance (8 B): 3 x 16 B per entry (the sweep also walks the source's row when it is a target, the
     // backward scan over a run of parallel edges re-reads cached lines: neither is counted).  A DAG vertex costs
     // ~72 B (two sort records of 12 B read and written, queue entry, row_ptr pair, count, offset, the 8-byte
-    // distance and the other outputs), an emitted predecessor 8 B (dense probe + store).
-    ctx.last.algorithmic_bytes = 32.0 * (double)rows + 48.0 * (double)mf + 72.0 * (double)nv + 8.0 * (double)ne;
+    // distance and the other outputs), an emitted predecessor 8 B (dense probe + store).  The edge-listing DAG
+    // adds the ordinal as the hop DAG's does: 4 B per walked entry in the fill pass, 4 B per emitted entry.
+    ctx.last.algorithmic_bytes = 32.0 * (double)rows + 48.0 * (double)mf + 72.0 * (double)nv + 8.0 * (double)ne +
+                                 (T::kEdges ? 4.0 * (double)mf + 4.0 * (double)ne : 0.0);
+}
+
+void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
+                   int64_t* farthest_out, bool edges) {
+    if (edges) sssp_kept_dag_t<TightEdgeDag>(g, target, max_distance, nv_out, ne_out, farthest_out);
+    else sssp_kept_dag_t<TightDag>(g, target, max_distance, nv_out, ne_out, farthest_out);
 }
 
 void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
@@ -809,6 +898,23 @@ void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_
         copy_d2h(&e, sh.wdag_off.get() + first + count, sizeof(int64_t), st);
         copy_d2h(pred_out, sh.wdag_pred.get() + b, (size_t)(e - b) * sizeof(int32_t), st);
     }
+}
+
+void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {
+    if (!(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag_read_edges: the graph was built without JG_ADJ_EDGE_INDEX");
+    if (g.wdag_nv < 0 || !g.wdag_edges)
+        fail(JG_ERR_STATE, "no edge-listing weighted predecessor DAG is held (jg_sssp_kept_dag_edges)");
+    if (first < 0 || count < 0 || first > g.wdag_nv || count > g.wdag_nv - first)
+        fail(JG_ERR_ARG, "range outside the DAG's vertices");
+    if (g.wdag_nv == 0 || count == 0 || !edge_out) return;
+    Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    hipStream_t st = sh.stream;
+    int64_t b = 0, e = 0;
+    copy_d2h(&b, sh.wdag_off.get() + first, sizeof(int64_t), st);
+    copy_d2h(&e, sh.wdag_off.get() + first + count, sizeof(int64_t), st);
+    copy_d2h(edge_out, sh.wdag_edge.get() + b, (size_t)(e - b) * sizeof(uint32_t), st);
 }
 
 }  // namespace jg

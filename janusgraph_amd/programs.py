@@ -154,7 +154,11 @@ class ShortestPathVertexProgram(VertexProgram):
     then bounds that sum, inclusive; edgeDirection("out" | "in" | "both") restricts the edges a path follows
     (default "both").  memory.getIteration() is 1 + the number of edges of the longest returned path (1 when
     there is none), with or without a distance property: this project's rule, not pinned by any reference
-    test."""
+    test.
+
+    includeEdges(True) returns each path as [vid, Edge, vid, ..., vid], the Edge objects being the graph's own:
+    two parallel edges between the same vertices give two paths.  It runs on the hop route only; together
+    with a distanceProperty it is refused (ValueError)."""
 
     SHORTEST_PATHS = "gremlin.shortestPathVertexProgram.shortestPaths"
     EDGE_DIRECTIONS = ("out", "in", "both")
@@ -165,9 +169,9 @@ class ShortestPathVertexProgram(VertexProgram):
         self.targets = conf.get("targets")  # None = every vertex
         self.max_distance = conf.get("maxDistance")
         self.include_edges = bool(conf.get("includeEdges", False))
-        if self.include_edges:
-            raise ValueError("includeEdges is not supported by GpuGraphComputer")
         self.distance_property = conf.get("distanceProperty")
+        if self.include_edges and self.distance_property is not None:
+            raise ValueError("includeEdges together with a distanceProperty is not supported by GpuGraphComputer")
         if self.distance_property is not None and (not isinstance(self.distance_property, str)
                                                    or not self.distance_property):
             raise ValueError("distanceProperty must name an edge property")
@@ -189,6 +193,10 @@ class ShortestPathVertexProgram(VertexProgram):
 
         def maxDistance(self, d):  # noqa: N802
             self.configuration["maxDistance"] = int(d)
+            return self
+
+        def includeEdges(self, include):  # noqa: N802
+            self.configuration["includeEdges"] = bool(include)
             return self
 
         def distanceProperty(self, key):  # noqa: N802
