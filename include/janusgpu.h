@@ -44,6 +44,8 @@
  *   jg_sssp_keep / jg_sssp_kept_dag
  *       TinkerPop ShortestPathVertexProgram with distanceProperty(key) and edgeDirection(dir) [TP-recall]:
  *       summed edge weights along the direction's edges, and the minimum-weight paths' predecessor DAG
+ *   jg_graph_set_weights_f64 / jg_sssp_keep_f64 / jg_sssp_kept_dag_f64
+ *       the same program over a Double distanceProperty: IEEE binary64 sums, exact ties only
  *   JG_ADJ_EDGE_INDEX / jg_bfs_kept_dag_edges / jg_sssp_kept_dag_edges
  *       the same program with includeEdges(true) [TP-recall]: a path is v, e, v, ..., v, so the snapshot numbers
  *       its edges and the DAGs list one entry per edge, parallel edges apart
@@ -79,7 +81,9 @@ extern "C" {
  * jg_cc_census_release added; jg_pagerank_top, jg_pagerank_top_read, jg_pagerank_top_release added;
  * jg_peer_pressure added; JG_ADJ_WEIGHT_BOTH, jg_sssp_keep, jg_sssp_kept_row, jg_sssp_kept_release,
  * jg_sssp_kept_dag, jg_sssp_kept_dag_read added; JG_ADJ_EDGE_INDEX, jg_graph_neighbor_edges,
- * jg_bfs_kept_dag_edges, jg_bfs_kept_dag_read_edges, jg_sssp_kept_dag_edges, jg_sssp_kept_dag_read_edges added. */
+ * jg_bfs_kept_dag_edges, jg_bfs_kept_dag_read_edges, jg_sssp_kept_dag_edges, jg_sssp_kept_dag_read_edges added;
+ * jg_graph_set_weights_f64, jg_sssp_keep_f64, jg_sssp_kept_row_f64, jg_sssp_kept_dag_f64,
+ * jg_sssp_kept_dag_edges_f64, jg_sssp_kept_dag_read_f64 added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -523,6 +527,62 @@ int jg_sssp_kept_dag_read(jg_graph* g, int64_t first, int64_t count, int32_t* ve
 int jg_sssp_kept_dag_edges(jg_graph* g, const uint8_t* target, int64_t max_distance /* < 0: none */,
                            int64_t* num_vertices_out, int64_t* num_entries_out, int64_t* farthest_out);
 int jg_sssp_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint32_t* edge_out);
+
+/* ---- the same over double edge weights (ShortestPathVertexProgram with a Double distanceProperty) ----
+ *
+ * Distance.  A path's length is the IEEE-754 binary64 sum of its edges' weights, added left to right from the
+ *   source, starting from +0.0; dist[v] is the smallest such sum.  fl(a + w) is monotone in a, so this is the
+ *   fixed point dist[v] = min over u of fl(dist[u] + w(u,v)) that the relaxation reaches, and what a host
+ *   Dijkstra over doubles computes, bit for bit.  Distances are held as their bit patterns: a non-negative
+ *   double read as a signed 64-bit integer orders as its value does, so the engine relaxes with the integer
+ *   atomicMin of jg_sssp_keep; no float atomic is used and nothing depends on arrival order.
+ * Tight edges.  u -> v with weight w is tight iff dist[u] is present, fl(dist[u] + w) == dist[v] as doubles and
+ *   dist[u] < dist[v].  No epsilon: 0.25 + 0.25 ties with a direct 0.5; 0.1 + 0.2 loses to a direct 0.3.
+ * Unreached: JG_DISTF_ABSENT (+Inf) in every double output.
+ *
+ * jg_graph_set_weights_f64: weight[m] = one double per edge of the edge list the graph was built from, in that
+ *   list's order.  The graph must have been built from ids (jg_graph_build, or a builder fed vertex / edge ids)
+ *   with JG_ADJ_EDGE_INDEX, hence on one shard; any other graph: JG_ERR_UNSUPPORTED.  m other than that list's
+ *   length, or a null array with m > 0: JG_ERR_ARG.  The array is uploaded, checked by one device reduction in a
+ *   fixed order (per-workgroup partials summed in workgroup order: the same statistics, automatic delta and
+ *   stats.levels on every run), and gathered beside every adjacency that was built (8 bytes per entry, counted
+ *   in jg_graph_info.device_bytes).
+ *     Every weight must be finite and > 0, else JG_ERR_ARG.
+ *     No relaxation may be absorbed (dist + w == dist would make the tight-edge graph cyclic): with rows = the
+ *     vertex count, wmin >= rows * wmax * 2^-52, wmin >= DBL_MIN and rows * wmax finite are required, else
+ *     JG_ERR_UNSUPPORTED (callers delegate).  Under that gate every relaxed edge strictly increases the distance
+ *     and no stored distance is infinite (jg_sssp.hip states the argument).
+ *   A second call replaces the weights and drops a kept f64 plane and its DAG; a failed call leaves the graph as
+ *   it was.  The int32 weights of the build, if any, are untouched.
+ * jg_sssp_keep_f64: jg_sssp_keep over those weights; direction, unknown source, stats and the one-shard rule as
+ *   there.  No absent marker exists on this route.  Without jg_graph_set_weights_f64, or without the relaxed
+ *   adjacency: JG_ERR_UNSUPPORTED.  JG_DIR_BOTH needs JG_ADJ_BOTH only (the doubles are gathered onto both
+ *   entries of an edge; JG_ADJ_WEIGHT_BOTH is not needed).  The automatic delta is 128 x the mean weight / the mean
+ *   degree, in double, at least wmin.  Its near passes relax each queued row from its distance as it stood
+ *   before the pass, so the plane and stats.levels (the near passes) are the same on every run; a threshold
+ *   change first tries T + delta and jumps to the far pile's exact minimum only when that bucket was empty.
+ *   The plane takes jg_sssp_keep's slot: a keep of
+ *   either kind drops the other's plane and DAG, jg_sssp_kept_release drops either.
+ * jg_sssp_kept_row_f64: dist_out[n] doubles in caller order.
+ * jg_sssp_kept_dag_f64 / jg_sssp_kept_dag_edges_f64 / jg_sssp_kept_dag_read_f64: as the integer calls, with the
+ *   tight-edge rule above.  max_distance is inclusive on the sum; < 0 or NaN: none.  farthest_out: -1.0 when no
+ *   target is reached.  Predecessors of v: each u with a tight entry once, at its first tight entry, in the
+ *   reverse row's order; the edge-listing twin lists every tight entry.  jg_sssp_kept_dag_read_edges serves both
+ *   kinds of edge-listing DAG.
+ * Kinds do not mix: jg_sssp_kept_row, jg_sssp_kept_dag, jg_sssp_kept_dag_edges on an f64 plane,
+ *   jg_sssp_kept_dag_read on an f64 DAG, and the _f64 calls on an integer plane or DAG: JG_ERR_STATE.
+ * Not covered (callers delegate): Float (binary32) properties, whose sums TinkerPop takes in float arithmetic;
+ *   Long weights beyond int32; graphs of several shards; graphs built from rows (the decoder skips doubles). */
+#define JG_DISTF_ABSENT (__builtin_huge_val()) /* +Inf (gcc, clang) */
+int jg_graph_set_weights_f64(jg_graph* g, const double* weight, int64_t m);
+int jg_sssp_keep_f64(jg_graph* g, int64_t source_vid, int32_t direction);
+int jg_sssp_kept_row_f64(jg_graph* g, double* dist_out);
+int jg_sssp_kept_dag_f64(jg_graph* g, const uint8_t* target, double max_distance /* < 0 or NaN: none */,
+                         int64_t* num_vertices_out, int64_t* num_entries_out, double* farthest_out);
+int jg_sssp_kept_dag_edges_f64(jg_graph* g, const uint8_t* target, double max_distance /* < 0 or NaN: none */,
+                               int64_t* num_vertices_out, int64_t* num_entries_out, double* farthest_out);
+int jg_sssp_kept_dag_read_f64(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, double* dist_out,
+                              int64_t* off_out, int32_t* pred_out);
 
 /* Adjacency of vertices rows[0, nrows) (output-order indices), in output-order indices: the host copy
  * of the snapshot a path walk-back reads where Fulgora re-reads each vertex's preloaded BOTH slice

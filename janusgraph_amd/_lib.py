@@ -55,6 +55,8 @@ EXPORTS = [
     "jg_sssp_keep", "jg_sssp_kept_row", "jg_sssp_kept_release", "jg_sssp_kept_dag", "jg_sssp_kept_dag_read",
     "jg_graph_neighbor_edges", "jg_bfs_kept_dag_edges", "jg_bfs_kept_dag_read_edges", "jg_sssp_kept_dag_edges",
     "jg_sssp_kept_dag_read_edges",
+    "jg_graph_set_weights_f64", "jg_sssp_keep_f64", "jg_sssp_kept_row_f64", "jg_sssp_kept_dag_f64",
+    "jg_sssp_kept_dag_edges_f64", "jg_sssp_kept_dag_read_f64",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -226,6 +228,12 @@ def load():
         "jg_bfs_kept_dag_read_edges": ([_P, _i64, _i64, _P], ctypes.c_int),
         "jg_sssp_kept_dag_edges": ([_P, _P, _i64, _P, _P, _P], ctypes.c_int),
         "jg_sssp_kept_dag_read_edges": ([_P, _i64, _i64, _P], ctypes.c_int),
+        "jg_graph_set_weights_f64": ([_P, _P, _i64], ctypes.c_int),
+        "jg_sssp_keep_f64": ([_P, _i64, _i32], ctypes.c_int),
+        "jg_sssp_kept_row_f64": ([_P, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_f64": ([_P, _P, ctypes.c_double, _P, _P, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_edges_f64": ([_P, _P, ctypes.c_double, _P, _P, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_read_f64": ([_P, _i64, _i64, _P, _P, _P, _P], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -817,6 +825,87 @@ class Graph:
             check(load().jg_sssp_kept_dag_read(self._h, first, last - first, None, None, None, into))
             first = last
         return vertex, dist, off, pred
+
+    # ---- the same over double weights (jg_graph_set_weights_f64): distances are float64, +inf = unreached ----
+
+    def set_weights_f64(self, weight):
+        """jg_graph_set_weights_f64: one double per edge of the edge list the graph was built from, in its order
+        (the graph needs ADJ_EDGE_INDEX).  Every weight finite and > 0; a range that could absorb a relaxation
+        is JG_ERR_UNSUPPORTED."""
+        w = np.ascontiguousarray(weight, np.float64)
+        if w.ndim != 1:
+            raise ValueError("weight needs one value per edge")
+        check(load().jg_graph_set_weights_f64(self._h, _ptr(w), len(w)))
+
+    def sssp_keep_f64(self, source, direction=DIR_BOTH):
+        """jg_sssp_keep_f64: sssp_keep over the weights of set_weights_f64 (DIR_BOTH needs ADJ_BOTH only)."""
+        check(load().jg_sssp_keep_f64(self._h, int(source), int(direction)))
+
+    def sssp_kept_row_f64(self, out=None):
+        """jg_sssp_kept_row_f64: the kept distances, into `out` (n float64) or a new array; +inf = unreached."""
+        if out is not None and not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.ndim == 1
+                                    and out.flags.c_contiguous and out.size >= self.n):
+            raise ValueError("out must be a C-contiguous float64 array of at least n elements")
+        row = self._out(self.n, np.float64) if out is None else out
+        check(load().jg_sssp_kept_row_f64(self._h, _ptr(row)))
+        return row
+
+    def _sssp_kept_dag_f64_call(self, fn, target, max_distance):
+        t = None
+        if target is not None:
+            t = np.ascontiguousarray(target, np.uint8)
+            if t.ndim != 1 or len(t) != self.n:
+                raise ValueError("target needs one flag per vertex")
+        nv, ne, far = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
+        md = -1.0 if max_distance is None else float(max_distance)
+        check(fn(self._h, _ptr(t), md, ctypes.byref(nv), ctypes.byref(ne), ctypes.byref(far)))
+        return nv.value, ne.value, far.value
+
+    def sssp_kept_dag_f64_build(self, target=None, max_distance=-1.0):
+        """jg_sssp_kept_dag_f64: as sssp_kept_dag_build over a plane of sssp_keep_f64 (max_distance: a float,
+        inclusive; < 0, NaN or None: no bound).  Returns (num_vertices, num_entries, farthest); farthest -1.0
+        when no target is reached."""
+        return self._sssp_kept_dag_f64_call(load().jg_sssp_kept_dag_f64, target, max_distance)
+
+    def sssp_kept_dag_edges_f64_build(self, target=None, max_distance=-1.0):
+        """jg_sssp_kept_dag_edges_f64: the edge-listing twin of sssp_kept_dag_f64_build."""
+        return self._sssp_kept_dag_f64_call(load().jg_sssp_kept_dag_edges_f64, target, max_distance)
+
+    def sssp_kept_dag_f64_read(self, first, count, want_pred=True):
+        """jg_sssp_kept_dag_read_f64, as sssp_kept_dag_read with float64 distances."""
+        vertex = np.empty(max(count, 1), np.int32)
+        dist = np.empty(max(count, 1), np.float64)
+        off = np.empty(count + 1, np.int64)
+        check(load().jg_sssp_kept_dag_read_f64(self._h, int(first), int(count), _ptr(vertex), _ptr(dist), _ptr(off), None))
+        pred = None
+        if want_pred:
+            k = int(off[-1] - off[0])
+            pred = np.empty(max(k, 1), np.int32)
+            check(load().jg_sssp_kept_dag_read_f64(self._h, int(first), int(count), None, None, None, _ptr(pred)))
+            pred = pred[:k]
+        return vertex[:count], dist[:count], off, pred
+
+    def sssp_kept_dag_f64(self, target=None, max_distance=-1.0):
+        """The minimum-weight-path predecessor DAG of the kept float64 distances (sssp_keep_f64): (vertex, dist,
+        off, pred) as sssp_kept_dag, an edge u -> v tight iff fl(dist[u] + w) == dist[v] exactly."""
+        nv, ne, _ = self.sssp_kept_dag_f64_build(target, max_distance)
+        if ne <= self.DAG_READ_ENTRIES:
+            return self.sssp_kept_dag_f64_read(0, nv)
+        vertex, dist, off, _ = self.sssp_kept_dag_f64_read(0, nv, want_pred=False)
+        pred = np.empty(ne, np.int32)
+        first = 0
+        while first < nv:
+            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
+            last = min(max(last, first + 1), nv)
+            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * int(off[first]))
+            check(load().jg_sssp_kept_dag_read_f64(self._h, first, last - first, None, None, None, into))
+            first = last
+        return vertex, dist, off, pred
+
+    def sssp_kept_dag_edges_f64(self, target=None, max_distance=-1.0):
+        """The edge-listing twin of sssp_kept_dag_f64: (vertex, dist, off, pred, edge)."""
+        nv, ne, _ = self.sssp_kept_dag_edges_f64_build(target, max_distance)
+        return self._dag_edge_ranges(self.sssp_kept_dag_f64_read, self.sssp_kept_dag_read_edges, nv, ne)
 
     def neighbors(self, rows, direction=DIR_BOTH):
         """jg_graph_neighbors: (off, nbr) CSR of the given output-order rows, in output-order indices."""

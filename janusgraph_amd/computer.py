@@ -355,7 +355,7 @@ class GpuGraphComputer:
             raise
         edges = self.graph.edges
         paths, max_level = [], 0
-        max_depth = -1 if vp.max_distance is None else vp.max_distance
+        max_depth = _int_bound(vp.max_distance)
         try:
             on_device = g.info()["num_shards"] == 1
             neighbors = g.neighbors if both else (lambda rows: g.neighbors(rows, reverse))
@@ -388,11 +388,15 @@ class GpuGraphComputer:
         the device (jg_sssp_keep, delta-stepping along edgeDirection), the tight-edge predecessor DAG to the
         targets within maxDistance (inclusive, on the summed weight) is built there (jg_sssp_kept_dag), and
         DevicePathDag enumerates it: sources in the given order, targets ascending, first predecessor first.
+        A float among the edges' values takes _f64_shortest_paths instead (a Double property).
         Refused (the caller delegates): an edge without the property or with a weight < 1 (zero-weight edges
         make the tight-edge graph cyclic; TinkerPop reads any Number), and graphs of several shards.
         The iteration count is 1 + the edges of the longest returned path (1 when there is none): what
         max_level + 1 means on the hop route; this project's rule, not pinned by any reference test."""
         direction = _PATH_DIRECTIONS[vp.edge_direction]
+        key = vp.distance_property
+        if any(isinstance(e.properties.get(key), (float, np.floating)) for e in self.graph.edges):
+            return self._f64_shortest_paths(ctx, vp)
         vid, src, dst, w = self.graph.snapshot(weight_property=vp.distance_property)
         if len(w) and int(w.min()) < 1:
             missing = int((w == _lib.WEIGHT_ABSENT).sum())
@@ -410,7 +414,7 @@ class GpuGraphComputer:
         g = ctx.build(vid, src, dst, w, flags=(_lib.ADJ_BOTH | _lib.ADJ_WEIGHT_BOTH) if both
                       else _lib.ADJ_IN | _lib.ADJ_OUT)
         paths, longest = [], 0
-        max_distance = -1 if vp.max_distance is None else vp.max_distance
+        max_distance = _int_bound(vp.max_distance)
         try:
             if g.info()["num_shards"] != 1:
                 raise ProgramNotSupported("ShortestPathVertexProgram with a distanceProperty is not run on a sharded "
@@ -419,6 +423,64 @@ class GpuGraphComputer:
             for s in sources:
                 g.sssp_keep(vid[s], direction)
                 got, _ = dag.paths(g.sssp_kept_dag(target, max_distance), s, target)
+                longest = max([longest] + [len(p) - 1 for p in got])
+                paths.extend([int(vid[x]) for x in p] for p in got)
+        finally:
+            g.close()
+        return vid, {}, longest + 1, {vp.SHORTEST_PATHS: paths}
+
+    def _f64_shortest_paths(self, ctx, vp):
+        """_weighted_shortest_paths when an edge's value for the key is a float (a Double property): a path's
+        length is the IEEE binary64 sum of its weights, ties are exact (jg_graph_set_weights_f64,
+        jg_sssp_keep_f64, jg_sssp_kept_dag_f64).  Every value must be a Python / numpy int (converted exactly;
+        refused beyond 2^53) or a float64.  Refused (the caller delegates): a missing property, a value of another
+        type (a binary32 Float among them: TinkerPop sums those in float arithmetic), a non-finite or <= 0 value,
+        weights whose range could absorb a relaxation (the library's JG_ERR_UNSUPPORTED), graphs of several
+        shards.  Path order and the iteration rule are _weighted_shortest_paths'."""
+        key = vp.distance_property
+
+        def refuse(why):
+            return ProgramNotSupported(f"ShortestPathVertexProgram with distanceProperty {key!r} is not run by "
+                                       f"GpuGraphComputer: {why}; delegate to FulgoraGraphComputer")
+
+        for e in self.graph.edges:
+            x = e.properties.get(key)
+            if x is None:
+                raise refuse("an edge lacks the property")
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.float64)):
+                raise refuse(f"a value of type {type(x).__name__}")
+            if isinstance(x, (int, np.integer)) and abs(int(x)) > 2**53:
+                raise refuse("an integer beyond 2^53 has no exact double")
+        direction = _PATH_DIRECTIONS[vp.edge_direction]
+        vid, src, dst, w = self.graph.snapshot(weight_property=key, float_weights=True)
+        if len(w) and not (np.isfinite(w).all() and w.min() > 0):
+            raise refuse("a weight is not finite and > 0")
+        index = {int(v): i for i, v in enumerate(vid.tolist())}
+        sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
+        target = None
+        if vp.targets is not None:
+            target = np.zeros(len(vid), bool)
+            target[[index[t] for t in vp.targets if t in index]] = True
+        both = direction == _lib.DIR_BOTH
+        try:
+            g = ctx.build(vid, src, dst, flags=(_lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT) | _lib.ADJ_EDGE_INDEX)
+        except _lib.JanusGpuError as e:
+            if e.code == _lib.JG_ERR_UNSUPPORTED:  # edge ordinals are kept on one shard only
+                raise refuse("the graph is sharded") from e
+            raise
+        paths, longest = [], 0
+        max_distance = -1.0 if vp.max_distance is None else float(vp.max_distance)
+        try:
+            try:
+                g.set_weights_f64(w)
+            except _lib.JanusGpuError as e:
+                if e.code == _lib.JG_ERR_UNSUPPORTED:
+                    raise refuse("the weights' range could absorb a relaxation") from e
+                raise
+            dag = DevicePathDag(len(vid))
+            for s in sources:
+                g.sssp_keep_f64(vid[s], direction)
+                got, _ = dag.paths(g.sssp_kept_dag_f64(target, max_distance), s, target)
                 longest = max([longest] + [len(p) - 1 for p in got])
                 paths.extend([int(vid[x]) for x in p] for p in got)
         finally:
@@ -435,6 +497,13 @@ class GpuGraphComputer:
                     v.properties.update(kv)
             return self.graph
         return ComputedGraph(self.graph, props)
+
+
+def _int_bound(d):
+    """maxDistance for the hop route and the integer weights' route: int(), -1 (none) for None, inf and NaN."""
+    if d is None or (isinstance(d, float) and not np.isfinite(d)):
+        return -1
+    return int(d)
 
 
 SOURCES_PER_BFS = 64  # jg_bfs_rows: one bit-parallel pass per 64 sources

@@ -1668,6 +1668,51 @@ int jg_sssp_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint3
     JG_GUARD_END
 }
 
+int jg_graph_set_weights_f64(jg_graph* g, const double* weight, int64_t m) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::graph_set_weights_f64(g->impl, weight, m);
+    JG_GUARD_END
+}
+
+int jg_sssp_keep_f64(jg_graph* g, int64_t source_vid, int32_t direction) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_keep_f64(g->impl, source_vid, direction);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_row_f64(jg_graph* g, double* dist_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g && dist_out, "null argument");
+    jg::sssp_kept_row_f64(g->impl, dist_out);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag_f64(jg_graph* g, const uint8_t* target, double max_distance, int64_t* num_vertices_out,
+                         int64_t* num_entries_out, double* farthest_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag_f64(g->impl, target, max_distance, num_vertices_out, num_entries_out, farthest_out, false);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag_edges_f64(jg_graph* g, const uint8_t* target, double max_distance, int64_t* num_vertices_out,
+                               int64_t* num_entries_out, double* farthest_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag_f64(g->impl, target, max_distance, num_vertices_out, num_entries_out, farthest_out, true);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag_read_f64(jg_graph* g, int64_t first, int64_t count, int32_t* vertex_out, double* dist_out,
+                              int64_t* off_out, int32_t* pred_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag_read_f64(g->impl, first, count, vertex_out, dist_out, off_out, pred_out);
+    JG_GUARD_END
+}
+
 int jg_graph_neighbors(const jg_graph* g, int32_t direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                        int64_t* nbr_out) {
     JG_GUARD_BEGIN

@@ -1137,6 +1137,7 @@ void build_graph_from_dense(Graph& g, DenseEdges& e) {
         fail(JG_ERR_UNSUPPORTED, "JG_ADJ_EDGE_INDEX: graphs of one shard only");
     if (keep_eidx && e.capped)
         fail(JG_ERR_UNSUPPORTED, "JG_ADJ_EDGE_INDEX: not under a query limit (the capped lists are not the caller's)");
+    g.edge_list_m = keep_eidx ? m : -1;
     bool first = true;
     for (size_t li = 0; li < g.shards.size(); ++li) {
         Shard& sh = *g.shards[li];

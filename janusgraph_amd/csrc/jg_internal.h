@@ -39,6 +39,9 @@ struct Csr {
     // optional (JG_ADJ_EDGE_INDEX): each entry's edge ordinal, its edge's position in the caller's edge list;
     // inside a run of equal columns ordinals ascend (a stable sort over entries selected in edge order)
     DevBuf<uint32_t> eidx;
+    // optional (jg_graph_set_weights_f64): each entry's double weight, gathered through eidx from the caller's
+    // per-edge array; never absent, every value finite and > 0
+    DevBuf<double> wf;
     // rows [empty_from, rows) have no entries (set with the pull plan: 1 + the last non-empty row;
     // -1 when unknown)
     mutable int64_t empty_from = -1;
@@ -50,7 +53,7 @@ struct Csr {
     mutable long long wstat[4] = {0, 0, 0, 0};  // sd_weight_stats: min, sum, count, max
     mutable bool wstat_ok = false;
     bool present() const { return row_ptr.size() > 0; }
-    int64_t bytes() const { return (int64_t)(row_ptr.bytes() + col.bytes() + weight.bytes() + eidx.bytes()); }
+    int64_t bytes() const { return (int64_t)(row_ptr.bytes() + col.bytes() + weight.bytes() + eidx.bytes() + wf.bytes()); }
 };
 
 // Degree-class plan for the pull kernels of one CSR on one shard.  Rows are sorted by degree
@@ -273,7 +276,9 @@ struct Shard {
     DevBuf<uint32_t> dag_edge;               // an edge-listing DAG's ordinals, parallel to dag_pred (Graph::dag_edges)
     // jg_sssp_keep's distance plane ([rows] int64, local row order, LLONG_MIN: absent) and the tight-edge
     // predecessor DAG of it (jg_sssp_kept_dag; Graph::wdag_nv vertices, distance descending): buffers of
-    // their own, so that a kept BFS row and its DAG can be held at the same time
+    // their own, so that a kept BFS row and its DAG can be held at the same time.  jg_sssp_keep_f64's plane and
+    // DAG take the same slots (Graph::sssp_f64, Graph::wdag_f64): the bit patterns of non-negative doubles,
+    // whose signed integer order is the distance order; +Inf's pattern: absent
     DevBuf<long long> sssp_dist;
     DevBuf<int32_t> wdag_vertex, wdag_pred;
     DevBuf<int64_t> wdag_dist, wdag_off;     // [wdag_nv], [wdag_nv + 1]
@@ -329,6 +334,14 @@ struct Graph {
     bool dag_edges = false;           // it lists edges (jg_bfs_kept_dag_edges): one entry per qualifying adjacency entry
     bool sssp_kept = false;           // jg_sssp_keep's plane is held (Shard::sssp_dist)
     int sssp_dir = 0;                 // its direction (jg_sssp_kept_dag reads the reverse adjacency)
+    bool sssp_f64 = false;            // the held plane is jg_sssp_keep_f64's (bit patterns of doubles)
+    bool wdag_f64 = false;            // the held weighted DAG was built from such a plane
+    // JG_ADJ_EDGE_INDEX: the length of the caller's edge list (what Csr::eidx indexes); -1 without the flag
+    int64_t edge_list_m = -1;
+    // jg_graph_set_weights_f64: the double weights are set (Csr::wf beside every built adjacency), and their
+    // smallest, largest and mean value (a fixed-order reduction: the same bits on every run)
+    bool has_wf = false;
+    double wf_min = 0, wf_max = 0, wf_mean = 0;
     int64_t wdag_nv = -1, wdag_ne = 0;  // the held weighted predecessor DAG (Shard::wdag_*); -1: none
     bool wdag_edges = false;            // it lists edges (jg_sssp_kept_dag_edges)
     int64_t census_listed = -1;       // the held component census (Shard::census_*); -1: none
@@ -615,6 +628,15 @@ void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_
                         int64_t* off_out, int32_t* pred_out);
 void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out);
 void sssp_kept_dag_drop(Graph& g);
+// jg_graph_set_weights_f64, jg_sssp_keep_f64, jg_sssp_kept_row_f64 (jg_sssp.hip) and the f64 flavours of the
+// weighted DAG (jg_pathdag.hip): distances travel as the bit patterns of doubles
+void graph_set_weights_f64(Graph& g, const double* weight, int64_t m);
+void sssp_keep_f64(Graph& g, int64_t source_vid, int direction);
+void sssp_kept_row_f64(Graph& g, double* dist_out);
+void sssp_kept_dag_f64(Graph& g, const uint8_t* target, double max_distance, int64_t* nv_out, int64_t* ne_out,
+                       double* farthest_out, bool edges);
+void sssp_kept_dag_read_f64(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, double* dist_out,
+                            int64_t* off_out, int32_t* pred_out);
 // The batches of the device-controlled loops (shortest distance's steps, the weighted DAG's rounds), whose
 // state the host reads once per batch: a first batch (the loop's own estimate), then 8, 16, ... 64 steps
 struct SdBatches {

@@ -32,6 +32,8 @@
 // de-duplication, so every qualifying entry of a run of parallel edges is listed, and the fill pass stores the
 // entry's edge ordinal (Csr::eidx, JG_ADJ_EDGE_INDEX) beside its predecessor.
 #include <climits>
+#include <cstring>
+#include <type_traits>
 
 #include "jg_frontier.h"
 #include "jg_internal.h"
@@ -203,8 +205,18 @@ struct HopEdgeDag {  // jg_bfs_kept_dag_edges: one level up, every entry (a self
         return a.dep[x] == a.depth[i] - 1;
     }
 };
+struct TightInt {  // the arithmetic of TightDag / TightEdgeDag, for the sweep
+    using W = int32_t;
+    static constexpr long long kAbsent = LLONG_MIN;
+    static __device__ __forceinline__ bool tight(long long du, int32_t w, long long dv) {
+        return w != INT32_MIN && du != LLONG_MIN && du + (long long)w == dv;
+    }
+    static const int32_t* weights(const Csr& c) { return c.weight.get(); }
+    static size_t weight_count(const Csr& c) { return c.weight.size(); }
+};
 struct TightDag {  // jg_sssp_kept_dag: a tight edge, the first of its weight in its equal-column run
     using Val = long long;
+    using Arith = TightInt;
     static constexpr bool kEdges = false;
     struct Extra {
         const int32_t* wt;
@@ -224,6 +236,7 @@ struct TightDag {  // jg_sssp_kept_dag: a tight edge, the first of its weight in
 };
 struct TightEdgeDag {  // jg_sssp_kept_dag_edges: every tight entry (weights are positive: a self-loop is never tight)
     using Val = long long;
+    using Arith = TightInt;
     static constexpr bool kEdges = true;
     using Extra = TightDag::Extra;
     template <class W>
@@ -231,6 +244,51 @@ struct TightEdgeDag {  // jg_sssp_kept_dag_edges: every tight entry (weights are
         const int32_t w = a.wt[p];
         const long long du = a.dep[x];
         return w != INT32_MIN && du != LLONG_MIN && du + (long long)w == a.depth[i];
+    }
+};
+
+// The f64 flavours (jg_sssp_kept_dag_f64, jg_sssp_kept_dag_edges_f64): the plane holds the bit patterns of
+// doubles >= 0 (+Inf's: absent), whose integer order is the distance order, so Val stays long long and seed, sweep,
+// sort and emit move the same 64-bit values; only the tight-edge predicate adds, in double.  u -> v with weight w
+// is tight iff dist[u] is present, dist[u] < dist[v] and fl(dist[u] + w) == dist[v], with no epsilon.
+constexpr long long kF64Absent = 0x7FF0000000000000ll;  // +Inf
+struct TightF64 {
+    using W = double;
+    static constexpr long long kAbsent = kF64Absent;
+    static __device__ __forceinline__ bool tight(long long du, double w, long long dv) {
+        // (patterns of non-negative doubles: equal patterns are equal doubles, and du < dv orders the doubles)
+        return du != kF64Absent && du < dv && __double_as_longlong(__longlong_as_double(du) + w) == dv;
+    }
+    static const double* weights(const Csr& c) { return c.wf.get(); }
+    static size_t weight_count(const Csr& c) { return c.wf.size(); }
+};
+struct TightDagF64 {  // a tight edge, the first tight entry of its equal-column run
+    using Val = long long;
+    using Arith = TightF64;
+    static constexpr bool kEdges = false;
+    struct Extra {
+        const double* wt;
+    };
+    // Two entries of one (v, u) run may both be tight with different weights (their sums round to the same
+    // double), so "the first of its weight" could list u twice: here an entry counts when no earlier entry of the
+    // run is tight (in integers the two rules agree).
+    template <class Wk>
+    static __device__ __forceinline__ bool counts(const Wk& a, int64_t i, int32_t x, int64_t p, int64_t k) {
+        const long long du = a.dep[x], dv = a.depth[i];
+        if (!TightF64::tight(du, a.wt[p], dv)) return false;
+        for (int64_t q = p - 1; q >= p - k && a.col[q] == x; --q)
+            if (TightF64::tight(du, a.wt[q], dv)) return false;
+        return true;
+    }
+};
+struct TightEdgeDagF64 {  // every tight entry (a self-loop has dist[u] == dist[v]: never tight)
+    using Val = long long;
+    using Arith = TightF64;
+    static constexpr bool kEdges = true;
+    using Extra = TightDagF64::Extra;
+    template <class Wk>
+    static __device__ __forceinline__ bool counts(const Wk& a, int64_t i, int32_t x, int64_t p, int64_t) {
+        return TightF64::tight(a.dep[x], a.wt[p], a.depth[i]);
     }
 };
 
@@ -356,7 +414,9 @@ __global__ __launch_bounds__(kBlock) void dag_fill_kernel(DagWalk<T> a) {
 // ---------------- the weighted DAG: seed and backward sweep by rounds ----------------
 
 // on[l] = row l is a target: a present distance, <= max_distance when that is >= 0, and its flag set;
-// *farthest = the largest distance of one (-1: none)
+// *farthest = the largest distance of one (-1: none).  kAbsent: the plane's "unreached" (an f64 plane's values,
+// its max_distance and farthest are bit patterns: the same compares)
+template <long long kAbsent>
 __global__ __launch_bounds__(kBlock) void wdag_seed_kernel(const long long* __restrict__ dist,
                                                            const int32_t* __restrict__ dense,
                                                            const uint8_t* __restrict__ target, int64_t rows,
@@ -366,7 +426,7 @@ __global__ __launch_bounds__(kBlock) void wdag_seed_kernel(const long long* __re
     long long m = -1;
     for (int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; l < rows; l += (int64_t)gridDim.x * blockDim.x) {
         const long long d = dist[l];
-        const bool t = d != LLONG_MIN && (max_distance < 0 || d <= max_distance) && (!target || target[dense[l]] != 0);
+        const bool t = d != kAbsent && (max_distance < 0 || d <= max_distance) && (!target || target[dense[l]] != 0);
         on[l] = t ? 1 : 0;
         if (t && d > m) m = d;
     }
@@ -386,10 +446,11 @@ __global__ __launch_bounds__(kBlock) void wdag_seed_kernel(const long long* __re
 // rounds there are is not known up front: the host enqueues them in batches (SdBatches) and reads the ring
 // once per batch; a round whose queue has no entries returns at once, and so does every round after it.
 constexpr int kWdRing = 4;
+template <class A>  // TightInt or TightF64
 struct WdagRound {
     const int64_t* rp;
     const int32_t* col;
-    const int32_t* wt;
+    const typename A::W* wt;
     const long long* dist;
     uint32_t* on;  // the `on` bytes as words (a byte is set with an atomic OR on its word)
     int32_t* vq;   // [rows] the rounds' queues, concatenated
@@ -409,7 +470,8 @@ __global__ void wdag_queue0_kernel(const int64_t* __restrict__ idx, int64_t nt, 
         len[j] = rp[l + 1] - rp[l];
     }
 }
-__global__ void wdag_ring0_kernel(WdagRound a, int64_t nt) {
+template <class A>
+__global__ void wdag_ring0_kernel(WdagRound<A> a, int64_t nt) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         for (int k = 0; k < kWdRing; ++k) a.packed[k] = 0ull, a.lbase[k] = 0;
         a.packed[0] = ((unsigned long long)nt << kPackShift) | (unsigned long long)a.qo[nt];
@@ -417,7 +479,8 @@ __global__ void wdag_ring0_kernel(WdagRound a, int64_t nt) {
     }
 }
 
-__global__ __launch_bounds__(kBlock) void wdag_round_kernel(WdagRound a) {
+template <class A>
+__global__ __launch_bounds__(kBlock) void wdag_round_kernel(WdagRound<A> a) {
     __shared__ WaveStage ws;
     const int cs = a.r % kWdRing, ns = (a.r + 1) % kWdRing;
     const unsigned long long pk = a.packed[cs];
@@ -455,9 +518,7 @@ __global__ __launch_bounds__(kBlock) void wdag_round_kernel(WdagRound a) {
                 const int32_t v = queue[cur.i];
                 const int64_t j = a.rp[v] + cur.row_offset(e);
                 u = a.col[j];
-                const int32_t w = a.wt[j];
-                const long long du = a.dist[u];
-                if (w != INT32_MIN && du != LLONG_MIN && du + (long long)w == a.dist[v]) {
+                if (A::tight(a.dist[u], a.wt[j], a.dist[v])) {
                     const uint32_t bit = 1u << ((u & 3) * 8);
                     if (!(a.on[u >> 2] & bit)) take = !(atomicOr(&a.on[u >> 2], bit) & bit);
                     if (take) deg = a.rp[u + 1] - a.rp[u];
@@ -703,19 +764,27 @@ void sssp_kept_dag_drop(Graph& g) {
     g.wdag_nv = -1;
     g.wdag_ne = 0;
     g.wdag_edges = false;
+    g.wdag_f64 = false;
 }
 
-// T: TightDag (jg_sssp_kept_dag) or TightEdgeDag (jg_sssp_kept_dag_edges), as bfs_kept_dag_t
+// T: TightDag (jg_sssp_kept_dag) or TightEdgeDag (jg_sssp_kept_dag_edges), as bfs_kept_dag_t; TightDagF64 /
+// TightEdgeDagF64 over a plane of jg_sssp_keep_f64, where max_distance and farthest are the doubles' bit patterns
+// (max_distance < 0: none; farthest -1: no target)
 template <class T>
 static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
                             int64_t* farthest_out) {
+    using A = typename T::Arith;
+    constexpr bool kF64 = std::is_same<A, TightF64>::value;
     if (T::kEdges && !(g.flags & JG_ADJ_EDGE_INDEX))
         fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag_edges: the graph was built without JG_ADJ_EDGE_INDEX");
     if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag runs on one shard");
     if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep)");
+    if (g.sssp_f64 != kF64)
+        fail(JG_ERR_STATE, kF64 ? "the kept plane holds integers (jg_sssp_keep): use jg_sssp_kept_dag"
+                                : "the kept plane holds doubles (jg_sssp_keep_f64): use jg_sssp_kept_dag_f64");
     Shard& sh = *g.shards[0];
     const Csr& c = reverse_csr(sh, g.sssp_dir);
-    if (!c.present() || c.weight.size() == 0)
+    if (!c.present() || A::weight_count(c) == 0)
         fail(JG_ERR_UNSUPPORTED,
              "jg_sssp_kept_dag reads the reverse of the kept direction's adjacency: not built, or built without weights");
     if (sh.rows != g.n || sh.dense_rows.size() < (size_t)std::max<int64_t>(sh.rows, 1))
@@ -732,6 +801,7 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
         g.wdag_nv = nv;
         g.wdag_ne = ne;
         g.wdag_edges = T::kEdges;
+        g.wdag_f64 = kF64;
         if (nv_out) *nv_out = nv;
         if (ne_out) *ne_out = ne;
         if (farthest_out) *farthest_out = farthest;
@@ -755,7 +825,7 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
     JG_HIP(hipMemsetAsync(on.get(), 0, on.bytes(), st));
     JG_HIP(hipMemsetAsync(d_far.get(), 0xff, sizeof(long long), st));
     uint8_t* on8 = reinterpret_cast<uint8_t*>(on.get());
-    wdag_seed_kernel<<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(dist, sh.dense_rows.get(), dtarget.get(), rows,
+    wdag_seed_kernel<A::kAbsent><<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(dist, sh.dense_rows.get(), dtarget.get(), rows,
                                                                      (long long)max_distance, on8, d_far.get());
     JG_LAUNCH_CHECK();
     DevBuf<int64_t> idx((size_t)rows), cpos, cscan;
@@ -779,12 +849,12 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
     DevBuf<int64_t> qo((size_t)rows + 1), len((size_t)rows);
     DevBuf<unsigned long long> ring((size_t)kWdRing + 1);
     DevBuf<int64_t> lbase((size_t)kWdRing);
-    WdagRound rd{c.row_ptr.get(), c.col.get(), c.weight.get(), dist, on.get(), vq.get(), qo.get(), ring.get(),
+    WdagRound<A> rd{c.row_ptr.get(), c.col.get(), A::weights(c), dist, on.get(), vq.get(), qo.get(), ring.get(),
                  lbase.get(), ring.get() + kWdRing, 0};
     wdag_queue0_kernel<<<grid_for(nt), kBlock, 0, st>>>(idx.get(), nt, c.row_ptr.get(), vq.get(), len.get());
     JG_LAUNCH_CHECK();
     prim::exclusive_scan(len.get(), qo.get(), nt, st);
-    wdag_ring0_kernel<<<1, kWave, 0, st>>>(rd, nt);
+    wdag_ring0_kernel<A><<<1, kWave, 0, st>>>(rd, nt);
     JG_LAUNCH_CHECK();
     const unsigned round_grid = grid_for(std::max<int64_t>(c.nnz / 4, rows), kBlock, 1024);
     int32_t r = 0;
@@ -793,7 +863,7 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
         if (r > (1 << 30)) fail(JG_ERR_STATE, "the weighted DAG's round control did not terminate");
         for (int k = 0, batch = b.take(); k < batch; ++k, ++r) {
             rd.r = r;
-            wdag_round_kernel<<<round_grid, kBlock, 0, st>>>(rd);
+            wdag_round_kernel<A><<<round_grid, kBlock, 0, st>>>(rd);
             JG_LAUNCH_CHECK();
         }
         copy_d2h(&pk, ring.get() + r % kWdRing, sizeof pk, st);
@@ -829,7 +899,7 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
     const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
     const size_t nr = (size_t)std::max<int64_t>(nranges, 1);
     DevBuf<int32_t> rfi(nr), rli(nr), rca(nr), rcl(nr);
-    DagWalk<T> wk{{c.weight.get()}, local.get(), wd, qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(),
+    DagWalk<T> wk{{A::weights(c)}, local.get(), wd, qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(),
                   dist, sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr,
                   nullptr, T::kEdges ? c.eidx.get() : nullptr, nullptr};
     const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
@@ -867,8 +937,9 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
     // ~72 B (two sort records of 12 B read and written, queue entry, row_ptr pair, count, offset, the 8-byte
     // distance and the other outputs), an emitted predecessor 8 B (dense probe + store).  The edge-listing DAG
     // adds the ordinal as the hop DAG's does: 4 B per walked entry in the fill pass, 4 B per emitted entry.
-    ctx.last.algorithmic_bytes = 32.0 * (double)rows + 48.0 * (double)mf + 72.0 * (double)nv + 8.0 * (double)ne +
-                                 (T::kEdges ? 4.0 * (double)mf + 4.0 * (double)ne : 0.0);
+    // The f64 flavours read an 8-byte weight: 3 x 20 B per entry.
+    ctx.last.algorithmic_bytes = 32.0 * (double)rows + (kF64 ? 60.0 : 48.0) * (double)mf + 72.0 * (double)nv +
+                                 8.0 * (double)ne + (T::kEdges ? 4.0 * (double)mf + 4.0 * (double)ne : 0.0);
 }
 
 void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_t* nv_out, int64_t* ne_out,
@@ -877,9 +948,29 @@ void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_
     else sssp_kept_dag_t<TightDag>(g, target, max_distance, nv_out, ne_out, farthest_out);
 }
 
-void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
-                        int64_t* off_out, int32_t* pred_out) {
-    if (g.wdag_nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag)");
+static int64_t f64_bits(double x) {
+    int64_t b;
+    std::memcpy(&b, &x, sizeof b);
+    return b;
+}
+
+void sssp_kept_dag_f64(Graph& g, const uint8_t* target, double max_distance, int64_t* nv_out, int64_t* ne_out,
+                       double* farthest_out, bool edges) {
+    // inclusive on the sum; < 0 or NaN: none (0 is +0.0's pattern, whichever zero came in)
+    const int64_t md = !(max_distance >= 0.0) ? -1 : max_distance == 0.0 ? 0 : f64_bits(max_distance);
+    int64_t far = -1;
+    if (edges) sssp_kept_dag_t<TightEdgeDagF64>(g, target, md, nv_out, ne_out, &far);
+    else sssp_kept_dag_t<TightDagF64>(g, target, md, nv_out, ne_out, &far);
+    if (farthest_out) {
+        double f = -1.0;
+        if (far >= 0) std::memcpy(&f, &far, sizeof f);
+        *farthest_out = f;
+    }
+}
+
+// the read of either kind of weighted DAG (dist_out: the distances as the DAG holds them, 8 bytes each)
+static void wdag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out, int64_t* off_out,
+                      int32_t* pred_out) {
     if (first < 0 || count < 0 || first > g.wdag_nv || count > g.wdag_nv - first)
         fail(JG_ERR_ARG, "range outside the DAG's vertices");
     if (g.wdag_nv == 0) {
@@ -898,6 +989,20 @@ void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_
         copy_d2h(&e, sh.wdag_off.get() + first + count, sizeof(int64_t), st);
         copy_d2h(pred_out, sh.wdag_pred.get() + b, (size_t)(e - b) * sizeof(int32_t), st);
     }
+}
+
+void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
+                        int64_t* off_out, int32_t* pred_out) {
+    if (g.wdag_nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag)");
+    if (g.wdag_f64) fail(JG_ERR_STATE, "the held weighted DAG has double distances: read it with jg_sssp_kept_dag_read_f64");
+    wdag_read(g, first, count, vertex_out, dist_out, off_out, pred_out);
+}
+
+void sssp_kept_dag_read_f64(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, double* dist_out,
+                            int64_t* off_out, int32_t* pred_out) {
+    if (g.wdag_nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag_f64)");
+    if (!g.wdag_f64) fail(JG_ERR_STATE, "the held weighted DAG has integer distances: read it with jg_sssp_kept_dag_read");
+    wdag_read(g, first, count, vertex_out, reinterpret_cast<int64_t*>(dist_out), off_out, pred_out);
 }
 
 void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {

@@ -13,6 +13,9 @@
 // jg_sssp_keep (sssp_keep, at the end): the delta-stepping engine over the adjacency of a direction, its
 //   distances left on the device for the weighted predecessor DAG of jg_pathdag.hip (ShortestPathVertexProgram
 //   with a distanceProperty).
+// jg_graph_set_weights_f64 / jg_sssp_keep_f64 (after it): the same engine over double weights, a third flavour of
+//   its templates (SdF64): distances as the bit patterns of non-negative doubles, the same integer atomicMin.
+#include <cfloat>
 #include <climits>
 #include <cmath>
 
@@ -38,17 +41,23 @@ constexpr int32_t kWeightAbsent = INT32_MIN;
 // a value-initialised take (nothing to append).
 // bdim (here and in the helpers below) is blockDim.x as the kernel reads it: there the compiler folds it to
 // the launch's uniform group size, in an inlined helper it stays a compare, a select and a load per wave.
-struct SdWalk {
+// W: the weights' type, int32 (kWeightAbsent: the edge lacks the property) or double (jg_sssp_keep_f64: the
+// weights of jg_graph_set_weights_f64, never absent).
+template <class W>
+struct SdWalkT {
     const int64_t* rp;
     const int32_t* col;
-    const int32_t* wt;  // null: unit weights
+    const W* wt;  // null: unit weights
     const int32_t* queue;
     const int64_t* qoff;
     int64_t nq, mf;
     int32_t* err;
 };
-template <class Relax, class Append>
-__device__ __forceinline__ void sd_relax_walk(const SdWalk& q, unsigned bdim, Relax&& relax, Append&& append) {
+using SdWalk = SdWalkT<int32_t>;
+__device__ __forceinline__ bool sd_weight_absent(int32_t w) { return w == kWeightAbsent; }
+__device__ __forceinline__ bool sd_weight_absent(double) { return false; }
+template <class W, class Relax, class Append>
+__device__ __forceinline__ void sd_relax_walk(const SdWalkT<W>& q, unsigned bdim, Relax&& relax, Append&& append) {
     const int64_t nthreads = (int64_t)gridDim.x * bdim;
     const int64_t tid = (int64_t)blockIdx.x * bdim + threadIdx.x;
     const int64_t per_tile = nthreads * kTdEdgesPerThread;
@@ -61,16 +70,16 @@ __device__ __forceinline__ void sd_relax_walk(const SdWalk& q, unsigned bdim, Re
 #pragma unroll
         for (int k = 0; k < kTdEdgesPerThread; ++k) {
             const int64_t e = e0 + k;
-            decltype(relax(0, 0, 0)) take{};
+            decltype(relax(0, 0, W(0))) take{};
             int32_t u = 0;
             if (e < q.mf) {
                 cur.advance(e);
                 const int32_t w = q.queue[cur.i];
                 const int64_t j = q.rp[w] + cur.row_offset(e);
                 u = q.col[j];
-                const int32_t wk = q.wt ? q.wt[j] : 1;
+                const W wk = q.wt ? q.wt[j] : W(1);
                 // the edge function would throw (ShortestDistanceVertexProgram.java:69)
-                if (wk == kWeightAbsent) *q.err = 1;
+                if (sd_weight_absent(wk)) *q.err = 1;
                 else take = relax(w, u, wk);
             }
             append(u, take);
@@ -234,12 +243,88 @@ template <class D> struct DistTraits;
 template <> struct DistTraits<long long> { static constexpr long long kNone = LLONG_MAX; };
 template <> struct DistTraits<unsigned int> { static constexpr unsigned int kNone = UINT_MAX; };
 
-template <class D>
+// The arithmetic of a run.  SdInt: integer distances and weights.  SdF64 (jg_sssp_keep_f64): the distances are
+// doubles >= 0 held as their bit patterns in a long long plane: such patterns order, as signed integers, exactly
+// as the doubles do, so the prefilter load, the atomicMin, the far-pile minimum and every threshold compare are
+// the integer ones and only the add (and the threshold's arithmetic) goes through double.  A threshold
+// (SdState::T) is held the same way.  No float atomic: nothing depends on the order candidates arrive in.
+struct SdInt {
+    using W = int32_t;
+    using Delta = long long;
+    template <class D> static constexpr __host__ __device__ D none() { return DistTraits<D>::kNone; }
+    static constexpr long long kPlaneAbsent = LLONG_MIN;
+    static constexpr bool kSync = false;  // a near pass relaxes a row from its distance as the lane finds it
+    static __device__ __forceinline__ long long add(long long d, int32_t w) { return d + (long long)w; }
+    static __host__ __device__ __forceinline__ long long first_threshold(long long delta) { return delta; }
+    // past the previous threshold by delta, or to the bucket of the smallest far distance m when that lies
+    // further (has_m: a far distance was seen)
+    static __device__ __forceinline__ long long next_threshold(long long T, bool, bool has_m, unsigned long long m,
+                                                               long long delta) {
+        long long t2 = T + delta;
+        if (has_m) {
+            const long long jump = ((long long)m / delta + 1) * delta;
+            t2 = jump > t2 ? jump : t2;
+        }
+        return t2;
+    }
+    static const int32_t* weights(const Csr& c) { return c.weight.get(); }
+};
+constexpr long long kF64InfBits = 0x7FF0000000000000ll;  // +Inf: unreached
+struct SdF64 {
+    using W = double;
+    using Delta = double;
+    // +Inf's pattern: above every finite distance, and an infinite candidate never replaces it
+    template <class D> static constexpr __host__ __device__ D none() { return (D)kF64InfBits; }
+    static constexpr long long kPlaneAbsent = kF64InfBits;
+    // The same distances come out of any interleaving, but how many near passes it takes does not: a lane that
+    // reads dist[w] while another lane lowers it relaxes from either value, and the far minimum the near passes
+    // collect holds whatever candidates happened to win.  This route promises the same stats.levels on every run,
+    // so its passes are synchronous: a pass relaxes its queue's rows from their distances as they stood before the
+    // pass (sd_snap_kernel copies them out first), which makes the distances after every pass, the next queue as
+    // a set and the rows of the far pile at or above the threshold functions of the input alone; and the
+    // threshold moves by the far pile's exact minimum only (below).
+    static constexpr bool kSync = true;
+    static __device__ __forceinline__ long long add(long long d, double w) {
+        return __double_as_longlong(__longlong_as_double(d) + w);
+    }
+    static __host__ __device__ __forceinline__ long long first_threshold(double delta) {
+        long long b;
+        __builtin_memcpy(&b, &delta, sizeof b);
+        return b;
+    }
+    // As SdInt's, in double: (floor(m / delta) + 1) * delta.  Rounding may leave that at or below m, or T + delta
+    // at T; the threshold must pass m (so that the split moves the row at m) and strictly rise, so it is
+    // lifted to the next double after m, or after T, where it does not.
+    // m is used only when the step before was itself a split (prev_split): then m is the smallest distance of
+    // the rows that split kept, read while no kernel changes a distance, the pile's exact minimum.  (What the
+    // near passes see on the way holds candidates that won an atomicMin and were beaten later: which of them
+    // do depends on timing, so SdF64's near pass does not collect them.)  A threshold change thus first tries
+    // T + delta and, when that bucket holds no row with entries, jumps with the next step.
+    static __device__ __forceinline__ long long next_threshold(long long T, bool prev_split, bool has_m,
+                                                               unsigned long long m, double delta) {
+        const double t = __longlong_as_double(T);
+        double t2 = t + delta;
+        long long b2 = __double_as_longlong(t2);
+        if (prev_split && has_m) {
+            const double dm = __longlong_as_double((long long)m);
+            const double jump = (floor(dm / delta) + 1.0) * delta;
+            t2 = jump > t2 ? jump : t2;
+            b2 = __double_as_longlong(t2);
+            if (b2 <= (long long)m) b2 = (long long)m + 1;  // the next double after m (m is finite)
+        }
+        if (b2 <= T) b2 = T + 1;
+        return b2 > kF64InfBits ? kF64InfBits : b2;
+    }
+    static const double* weights(const Csr& c) { return c.wf.get(); }
+};
+
+template <class D, class A = SdInt>
 struct SdStep {
     const int64_t* rp;
     const int32_t* col;
-    const int32_t* wt;
-    D* dist;                    // DistTraits<D>::kNone: unreached
+    const typename A::W* wt;
+    D* dist;                    // A::none<D>(): unreached
+    D* snap;                    // A::kSync: the near queue's rows' distances before the pass (by row); else null
     int32_t* nq[2];             // near queues: step s relaxes nq[s & 1] (and its first-edge offsets qo),
     int64_t* qo[2];             // its near pass appends to nq[(s + 1) & 1]
     unsigned long long* nctr;   // [kSdRing] step s's near queue as the near pass before it left it, packed
@@ -253,7 +338,7 @@ struct SdStep {
     SdState* st;                // [kSdRing]
     unsigned long long* passes; // near passes run (a near queue with rows)
     int32_t* err;
-    long long delta;
+    typename A::Delta delta;
     int32_t step;
 };
 
@@ -267,8 +352,8 @@ struct SdStep {
 // here), and fsz[p.fc] (step s's split appends to fsz[p.fc ^ 1]; its near pass runs after every split
 // workgroup has decided).  A split that appended to nctr[s] let a late workgroup see entries, decide
 // "no split" and leave its part of the far pile where it was.
-template <class D>
-__device__ SdState sd_decide(const SdStep<D>& a) {
+template <class D, class A>
+__device__ SdState sd_decide(const SdStep<D, A>& a) {
     const int ps = (a.step + kSdRing - 1) % kSdRing;
     const SdState p = a.st[ps];
     SdState c = p;
@@ -280,13 +365,8 @@ __device__ SdState sd_decide(const SdStep<D>& a) {
         c.end_step = a.step;
         return c;
     }
-    long long t2 = p.T + a.delta;
     const unsigned long long m = a.fmin[ps];
-    if (m != ULLONG_MAX) {
-        const long long jump = ((long long)m / a.delta + 1) * a.delta;
-        t2 = jump > t2 ? jump : t2;
-    }
-    c.T = t2;
+    c.T = A::next_threshold(p.T, p.split != 0, m != ULLONG_MAX, m, a.delta);
     c.fc = p.fc ^ 1;
     c.split = 1;
     return c;
@@ -295,8 +375,8 @@ __device__ SdState sd_decide(const SdStep<D>& a) {
 // The far pile at a threshold change: rows now below T join the step's near queue, rows below the previous
 // threshold were relaxed at their final distance already (dropped), the others stay (their smallest
 // distance goes to fmin[step]).
-template <class D>
-__global__ __launch_bounds__(kBlock) void sd_split_kernel(SdStep<D> a) {
+template <class D, class A>
+__global__ __launch_bounds__(kBlock) void sd_split_kernel(SdStep<D, A> a) {
     __shared__ SdState s_st;
     __shared__ long long s_tprev;
     __shared__ WaveStage ws;
@@ -349,8 +429,8 @@ __global__ __launch_bounds__(kBlock) void sd_split_kernel(SdStep<D> a) {
 // count is kept, for `passes`).  Block 0 also keeps the rings: the next step's output counters and far
 // minimum start empty, the far minimum carries over a step without a split, and after a split the emptied
 // pile's size is reset.
-template <class D>
-__global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
+template <class D, class A>
+__global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D, A> a) {
     __shared__ SdState s_st;
     __shared__ long long s_nq, s_mf;
     __shared__ WaveStage ws;
@@ -366,7 +446,7 @@ __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
             a.sctr[(a.step + 2) % kSdRing] = 0ull;
             a.fmin[(a.step + 2) % kSdRing] = ULLONG_MAX;
             if (s_st.split) a.fsz[s_st.fc ^ 1] = 0ull;
-            else atomicMin(a.fmin + cs, a.fmin[(a.step + kSdRing - 1) % kSdRing]);
+            else if (!A::kSync) atomicMin(a.fmin + cs, a.fmin[(a.step + kSdRing - 1) % kSdRing]);
             if (s_nq + left > 0) a.passes[0] += 1;  // (as the host-driven passes counted: a queue with rows)
         }
     }
@@ -386,11 +466,11 @@ __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
     unsigned long long fm = ULLONG_MAX;  // this lane's smallest distance that stays in the far pile
     struct Take { bool to_near, to_far; int64_t du; };  // where a relaxed row goes (du: its push degree)
     sd_relax_walk(
-        SdWalk{a.rp, a.col, a.wt, near, qoff, nq, mf, a.err}, blockDim.x,
-        [&](int32_t w, int32_t u, int32_t wk) {
+        SdWalkT<typename A::W>{a.rp, a.col, a.wt, near, qoff, nq, mf, a.err}, blockDim.x,
+        [&](int32_t w, int32_t u, typename A::W wk) {
             Take r{};
             // dist[w] now: it only fell since w was queued
-            const long long nd = (long long)a.dist[w] + (long long)wk;
+            const long long nd = A::add((long long)(A::kSync ? a.snap[w] : a.dist[w]), wk);
             // the prefilter reads past L1 (agent scope): a hub row's entry is hit from every XCD at
             // once, and a stale L1 copy would send each of those lanes to the atomic
             if (nd < (long long)__hip_atomic_load(&a.dist[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &&
@@ -415,7 +495,23 @@ __global__ __launch_bounds__(kBlock) void sd_near_kernel(SdStep<D> a) {
         const unsigned long long x = __shfl_xor(fm, o, kWave);
         fm = x < fm ? x : fm;
     }
-    if (lane_id() == 0 && fm != ULLONG_MAX) atomicMin(a.fmin + cs, fm);
+    if (!A::kSync && lane_id() == 0 && fm != ULLONG_MAX) atomicMin(a.fmin + cs, fm);
+}
+
+// A::kSync: the distances of the step's near queue's rows as they stand before its near pass (between the step's
+// split and near kernels; the queue and its size as sd_near_kernel finds them)
+template <class D, class A>
+__global__ __launch_bounds__(kBlock) void sd_snap_kernel(SdStep<D, A> a) {
+    const int cs = a.step % kSdRing;
+    const SdState st = a.st[cs];
+    if (st.done) return;
+    const unsigned long long h = st.split ? a.sctr[cs] : a.nctr[cs];
+    const int64_t nq = (int64_t)(h >> kPackShift);
+    const int32_t* __restrict__ near = a.nq[a.step & 1];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t w = near[i];
+        a.snap[w] = a.dist[w];
+    }
 }
 
 // The superstep start: distances absent, best empty, the seed at 0 as superstep 1's frontier.
@@ -440,10 +536,10 @@ __global__ void sd_super_init_kernel(SdPush a, int64_t rows, int32_t seed) {
 
 // The start: every row unreached, no stamps or far flags, the seed at 0 as step 0's near queue, the ring
 // empty, the state before step 0: threshold delta, far pile 0.
-template <class D>
-__global__ void sd_init_kernel(SdStep<D> a, int64_t rows, int32_t seed, long long delta) {
+template <class D, class A>
+__global__ void sd_init_kernel(SdStep<D, A> a, int64_t rows, int32_t seed) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
-        a.dist[i] = i == seed ? (D)0 : DistTraits<D>::kNone;
+        a.dist[i] = i == seed ? (D)0 : A::template none<D>();
         a.stamp[i] = 0;
         a.far_flag[i] = 0;
     }
@@ -458,7 +554,7 @@ __global__ void sd_init_kernel(SdStep<D> a, int64_t rows, int32_t seed, long lon
         a.passes[0] = 0ull;
         *a.err = 0;
         SdState s0{};
-        s0.T = delta;
+        s0.T = A::first_threshold(a.delta);
         a.st[kSdRing - 1] = s0;
     }
 }
@@ -752,11 +848,11 @@ long long sd_auto_delta(const long long* ws, int64_t nnz, int64_t rows) {
 
 // The kept plane of a run (jg_sssp_keep): int64 in local row order, LLONG_MIN where the run's own plane has
 // "unreached"
-template <class D>
+template <class D, class A>
 __global__ void sd_widen_kernel(const D* __restrict__ dist, int64_t rows, long long* __restrict__ plane) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {
         const D d = dist[i];
-        plane[i] = d == DistTraits<D>::kNone ? LLONG_MIN : (long long)d;
+        plane[i] = d == A::template none<D>() ? A::kPlaneAbsent : (long long)d;
     }
 }
 
@@ -764,8 +860,8 @@ __global__ void sd_widen_kernel(const D* __restrict__ dist, int64_t rows, long l
 // it relaxes; see sd_near_kernel).  host[] (nullable) gets the distances (INT64_MIN: absent), plane
 // (nullable, on the device, [rows]) the same in local row order, written before end_ev; end_ev is recorded
 // once the distances are final, before they are copied out.  Returns the near passes run.
-template <class D>
-int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, long long delta, int64_t* host, long long* plane,
+template <class D, class A = SdInt>
+int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, typename A::Delta delta, int64_t* host, long long* plane,
                         hipEvent_t end_ev) {
     hipStream_t s = sh.stream;
     const int64_t rows = sh.rows, cap = std::max<int64_t>(rows, 1);
@@ -776,11 +872,13 @@ int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, long long delta, 
     DevBuf<int32_t> stamp(cap), far_flag(cap), err(1);
     DevBuf<unsigned long long> ring(3 * kSdRing + 3);  // nctr[kSdRing], fmin[kSdRing], fsz[2], passes, sctr[kSdRing]
     DevBuf<SdState> st(kSdRing);
-    SdStep<D> a{};
+    SdStep<D, A> a{};
     a.rp = c.row_ptr.get();
     a.col = c.col.get();
-    a.wt = c.weight.get();
+    a.wt = A::weights(c);
     a.dist = dist.get();
+    DevBuf<D> snap(A::kSync ? cap : 0);
+    a.snap = snap.get();
     for (int k = 0; k < 2; ++k) {
         a.nq[k] = nq[k].get();
         a.qo[k] = qo[k].get();
@@ -796,7 +894,7 @@ int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, long long delta, 
     a.st = st.get();
     a.err = err.get();
     a.delta = delta;
-    sd_init_kernel<D><<<grid_for(rows), kBlock, 0, s>>>(a, rows, (int32_t)seed, delta);
+    sd_init_kernel<D, A><<<grid_for(rows), kBlock, 0, s>>>(a, rows, (int32_t)seed);
     JG_LAUNCH_CHECK();
     // Fixed grids (the host does not know a pass's size): the near pass grid-strides over its edges, a
     // workgroup whose slice of a tile is past the end leaves at once.  tools/sd_bench.py, weights 1..255,
@@ -813,16 +911,20 @@ int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, long long delta, 
         if (step > (1 << 26)) fail(JG_ERR_STATE, "delta-stepping control did not terminate");
         for (int k = 0, batch = b.take(); k < batch; ++k, ++step) {
             a.step = step;
-            sd_split_kernel<D><<<split_grid, kBlock, 0, s>>>(a);
+            sd_split_kernel<D, A><<<split_grid, kBlock, 0, s>>>(a);
             JG_LAUNCH_CHECK();
-            sd_near_kernel<D><<<near_grid, kBlock, 0, s>>>(a);
+            if (A::kSync) {
+                sd_snap_kernel<D, A><<<split_grid, kBlock, 0, s>>>(a);
+                JG_LAUNCH_CHECK();
+            }
+            sd_near_kernel<D, A><<<near_grid, kBlock, 0, s>>>(a);
             JG_LAUNCH_CHECK();
         }
         copy_d2h(&hs, st.get() + (step - 1) % kSdRing, sizeof hs, s);
         if (hs.done) break;
     }
     if (plane && rows) {
-        sd_widen_kernel<D><<<grid_for(rows), kBlock, 0, s>>>(dist.get(), rows, plane);
+        sd_widen_kernel<D, A><<<grid_for(rows), kBlock, 0, s>>>(dist.get(), rows, plane);
         JG_LAUNCH_CHECK();
     }
     JG_HIP(hipEventRecord(end_ev, s));  // the distances are final: their copy-out is the caller's
@@ -836,7 +938,7 @@ int sd_delta_stepping_t(Shard& sh, const Csr& c, int64_t seed, long long delta, 
     if (host) {
         std::vector<D> hd(rows);
         if (rows) copy_d2h(hd.data(), dist.get(), rows * sizeof(D), s);
-        for (int64_t l = 0; l < rows; ++l) host[l] = hd[l] == DistTraits<D>::kNone ? LLONG_MIN : (int64_t)hd[l];
+        for (int64_t l = 0; l < rows; ++l) host[l] = hd[l] == A::template none<D>() ? LLONG_MIN : (int64_t)hd[l];
     }
     int32_t e = 0;
     copy_d2h(&e, err.get(), sizeof e, s);
@@ -970,6 +1072,7 @@ void sssp_kept_release(Graph& g) {
         sp->sssp_dist.reset();
     }
     g.sssp_kept = false;
+    g.sssp_f64 = false;
 }
 
 // Shortest summed weights from one source along `direction`, by the delta-stepping of jg_shortest_distance
@@ -1024,6 +1127,204 @@ void sssp_keep(Graph& g, int64_t source_vid, int direction) {
 
 void sssp_kept_row(Graph& g, int64_t* dist_out) {
     if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep)");
+    if (g.sssp_f64) fail(JG_ERR_STATE, "the kept plane holds doubles (jg_sssp_keep_f64): read it with jg_sssp_kept_row_f64");
+    Shard& sh = *g.shards[0];
+    rows_to_dense(g, sh, sh.sssp_dist.get(), reinterpret_cast<long long*>(dist_out));
+}
+
+// ---------------- double weights: jg_graph_set_weights_f64, jg_sssp_keep_f64 ----------------
+
+namespace {
+
+// The weights' statistics, one partial per workgroup: the smallest, largest and summed value of the workgroup's
+// share (a fixed grid-stride assignment, reduced in a fixed order: lanes by a butterfly, waves in wave order) and
+// how many values are not finite and > 0.  The host sums the partials in workgroup order, so the statistics, the
+// automatic delta and with it stats.levels are the same on every run.  No atomic.
+struct WfPart {
+    double mn, mx, sum;
+    unsigned long long bad;
+};
+constexpr int kWfGrid = 1024;
+__global__ __launch_bounds__(kBlock) void wf_stats_kernel(const double* __restrict__ w, int64_t m, WfPart* __restrict__ part) {
+    __shared__ WfPart red[kBlock / kWave];
+    double mn = __builtin_huge_val(), mx = 0.0, sum = 0.0;
+    unsigned long long bad = 0;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (int64_t)gridDim.x * blockDim.x) {
+        const double x = w[j];
+        if (!(x > 0.0) || !(x < __builtin_huge_val())) {  // zero, negative, NaN, +Inf
+            ++bad;
+            continue;
+        }
+        mn = x < mn ? x : mn;
+        mx = x > mx ? x : mx;
+        sum += x;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const double a = __shfl_xor(mn, o, kWave), b = __shfl_xor(mx, o, kWave);
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+        sum += __shfl_xor(sum, o, kWave);
+        bad += __shfl_xor(bad, o, kWave);
+    }
+    if (lane_id() == 0) red[wave_id()] = WfPart{mn, mx, sum, bad};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        WfPart r = red[0];
+        for (int k = 1; k < kBlock / kWave; ++k) {
+            r.mn = red[k].mn < r.mn ? red[k].mn : r.mn;
+            r.mx = red[k].mx > r.mx ? red[k].mx : r.mx;
+            r.sum += red[k].sum;
+            r.bad += red[k].bad;
+        }
+        part[blockIdx.x] = r;
+    }
+}
+
+// wf[j] = weight[eidx[j]]: each entry's double, through its edge ordinal (as csr_finish gathers the int32 weights)
+__global__ void wf_gather_kernel(const double* __restrict__ w, const uint32_t* __restrict__ eidx, int64_t nnz,
+                                 double* __restrict__ wf) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nnz; j += (int64_t)gridDim.x * blockDim.x)
+        wf[j] = w[eidx[j]];
+}
+
+}  // namespace
+
+// The gate: with n = the vertex count, wmin >= n * wmax * 2^-52, wmin >= DBL_MIN and n * wmax finite.
+// Why no relaxation is absorbed under it.  A row's first stored distance is the left-to-right sum of the weights
+// along the first-touch tree's path to it: at most n - 1 weights (the tree has no cycle), each at most wmax, each
+// add rounding up by at most a factor 1 + 2^-53; every later stored distance of the row is smaller (the atomicMin
+// only lets a distance fall, and fl(a + w) is monotone in a).  So a stored distance d is below
+// n * wmax * (1 + 2^-53)^n < n * wmax * (1 + 2^-21) for n < 2^31.  d is 0 (the source: fl(0 + w) = w > 0) or at
+// least wmin >= DBL_MIN, hence normal, and the gap from a normal d to the next double is at most d * 2^-52.  The
+// gate's product is rounded once (by at most 1 - 2^-53), so half that gap, d * 2^-53, is below
+// n * wmax * (1 + 2^-21) * 2^-53 < fl(n * wmax) * 2^-52 <= wmin <= w: d + w lies past the midpoint to the next
+// double and fl(d + w) > d.  Every relaxed edge therefore strictly increases the distance: a tight edge u -> v has
+// dist[u] < dist[v], and the tight-edge graph has no cycle.
+// No stored distance is infinite: unreached is +Inf's own pattern, so a candidate that overflowed to +Inf is
+// never below what a row holds and the atomicMin never sees it (with n * wmax finite none arises but in the
+// last binade).
+void graph_set_weights_f64(Graph& g, const double* weight, int64_t m) {
+    if (!(g.flags & JG_ADJ_EDGE_INDEX) || g.edge_list_m < 0)
+        fail(JG_ERR_UNSUPPORTED,
+             "jg_graph_set_weights_f64 needs a graph built from ids with JG_ADJ_EDGE_INDEX (its entries' edge ordinals)");
+    if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_graph_set_weights_f64: graphs of one shard only");
+    if (m != g.edge_list_m) fail(JG_ERR_ARG, "jg_graph_set_weights_f64: m is not the length of the edge list the graph was built from");
+    if (m > 0 && !weight) fail(JG_ERR_ARG, "weight is null");
+    Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    hipStream_t s = sh.stream;
+    DevBuf<double> dw((size_t)std::max<int64_t>(m, 1));
+    double wmin = 0, wmax = 0, mean = 0;
+    if (m > 0) {
+        copy_h2d(dw.get(), weight, (size_t)m * sizeof(double), s);
+        const unsigned grid = grid_for(m, kBlock, kWfGrid);
+        DevBuf<WfPart> part(grid);
+        wf_stats_kernel<<<grid, kBlock, 0, s>>>(dw.get(), m, part.get());
+        JG_LAUNCH_CHECK();
+        std::vector<WfPart> hp(grid);
+        copy_d2h(hp.data(), part.get(), grid * sizeof(WfPart), s);
+        WfPart r = hp[0];
+        for (unsigned k = 1; k < grid; ++k) {  // workgroup order
+            r.mn = hp[k].mn < r.mn ? hp[k].mn : r.mn;
+            r.mx = hp[k].mx > r.mx ? hp[k].mx : r.mx;
+            r.sum += hp[k].sum;
+            r.bad += hp[k].bad;
+        }
+        if (r.bad) fail(JG_ERR_ARG, "jg_graph_set_weights_f64: every weight must be finite and > 0");
+        wmin = r.mn;
+        wmax = r.mx;
+        mean = std::isfinite(r.sum) ? r.sum / (double)m : wmax;  // (a sum past DBL_MAX: any delta is correct)
+        const double span = (double)std::max<int64_t>(g.n, 1) * wmax;
+        if (!std::isfinite(span) || wmin < DBL_MIN || wmin < span * 0x1p-52)
+            fail(JG_ERR_UNSUPPORTED,
+                 "jg_graph_set_weights_f64: the weights' range lets a relaxation be absorbed (needs wmin >= rows * wmax * 2^-52, "
+                 "wmin >= DBL_MIN, rows * wmax finite)");
+    }
+    // gathered beside every built adjacency, into buffers of their own: a failure up to here left the graph as it was
+    Csr* cs[3] = {&sh.out, &sh.in, &sh.both};
+    DevBuf<double> nw[3];
+    for (int k = 0; k < 3; ++k) {
+        const Csr& c = *cs[k];
+        if (!c.present()) continue;
+        if (c.eidx.size() < (size_t)c.nnz) fail(JG_ERR_STATE, "jg_graph_set_weights_f64: an adjacency holds no edge ordinals");
+        nw[k].alloc((size_t)std::max<int64_t>(c.nnz, 1));
+        if (c.nnz > 0) {
+            wf_gather_kernel<<<grid_for(c.nnz), kBlock, 0, s>>>(dw.get(), c.eidx.get(), c.nnz, nw[k].get());
+            JG_LAUNCH_CHECK();
+        }
+    }
+    JG_HIP(hipStreamSynchronize(s));
+    if (g.sssp_kept && g.sssp_f64) sssp_kept_release(g);  // distances of the weights that leave
+    int64_t before = 0, after = 0;
+    for (int k = 0; k < 3; ++k) {
+        before += (int64_t)cs[k]->wf.bytes();
+        cs[k]->wf.swap(nw[k]);
+        after += (int64_t)cs[k]->wf.bytes();
+    }
+    g.info.device_bytes += after - before;
+    g.has_wf = true;
+    g.wf_min = wmin;
+    g.wf_max = wmax;
+    g.wf_mean = mean;
+}
+
+// jg_sssp_keep over the double weights: the same engine with SdF64's arithmetic, the plane (bit patterns, +Inf:
+// unreached) in jg_sssp_keep's slot.  delta: Tune::sd_delta when set, else kSdDeltaScale x the mean weight / the
+// mean degree in double, at least wmin.
+void sssp_keep_f64(Graph& g, int64_t source_vid, int direction) {
+    if (direction < JG_DIR_OUT || direction > JG_DIR_BOTH) fail(JG_ERR_ARG, "bad direction");
+    if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_sssp_keep_f64 runs on one shard");
+    sssp_kept_release(g);
+    Ctx& ctx = *g.ctx;
+    ctx.last = jg_stats{};
+    Shard& sh = *g.shards[0];
+    const Csr& c = direction == JG_DIR_BOTH ? sh.both : direction == JG_DIR_OUT ? sh.out : sh.in;
+    if (!g.has_wf) fail(JG_ERR_UNSUPPORTED, "jg_sssp_keep_f64 needs jg_graph_set_weights_f64 first");
+    if (!c.present() || c.wf.size() == 0)
+        fail(JG_ERR_UNSUPPORTED, "jg_sssp_keep_f64: the adjacency of that direction was not built");
+    DeviceGuard dg(sh);
+    hipStream_t s = sh.stream;
+    const int64_t rows = sh.rows;
+    double delta = 1.0;
+    if (tune().sd_delta > 0) {
+        delta = (double)tune().sd_delta;
+    } else if (c.nnz > 0 && g.wf_mean > 0) {
+        const double mean_deg = std::max(1.0, (double)c.nnz / (double)std::max<int64_t>(rows, 1));
+        delta = std::max(g.wf_min, kSdDeltaScale * g.wf_mean / mean_deg);
+        if (!std::isfinite(delta)) delta = g.wf_max;
+    }
+    int shard = 0;
+    const int64_t seed = local_of_vid(g, source_vid, &shard);
+    DevBuf<long long> plane((size_t)std::max<int64_t>(rows, 1));
+    Event t0, t1;
+    region_mark(s, true);
+    JG_HIP(hipEventRecord(t0, s));
+    int levels = 0;
+    if (seed < 0) {  // not a vertex: every distance absent
+        if (rows) {
+            fill_ll_kernel<<<grid_for(rows), kBlock, 0, s>>>(plane.get(), rows, kF64InfBits);
+            JG_LAUNCH_CHECK();
+        }
+        JG_HIP(hipEventRecord(t1, s));
+        region_mark(s, false);
+    } else {
+        levels = sd_delta_stepping_t<long long, SdF64>(sh, c, seed, delta, nullptr, plane.get(), t1);
+    }
+    JG_HIP(hipEventSynchronize(t1));
+    float ms = 0;
+    JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    ctx.last.compute_ms = ms;
+    ctx.last.levels = levels;
+    sh.sssp_dist.swap(plane);
+    g.sssp_kept = true;
+    g.sssp_f64 = true;
+    g.sssp_dir = direction;
+}
+
+void sssp_kept_row_f64(Graph& g, double* dist_out) {
+    if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep_f64)");
+    if (!g.sssp_f64) fail(JG_ERR_STATE, "the kept plane holds integers (jg_sssp_keep): read it with jg_sssp_kept_row");
     Shard& sh = *g.shards[0];
     rows_to_dense(g, sh, sh.sssp_dist.get(), reinterpret_cast<long long*>(dist_out));
 }

@@ -74,15 +74,20 @@ class InMemoryGraph:
         return self.vertices[int(vid)]
 
     # --- OLAP snapshot ---
-    def snapshot(self, weight_property: str | None = None):
+    def snapshot(self, weight_property: str | None = None, *, float_weights: bool = False):
         """(vid, src, dst, weight): existing vertices + every stored edge (ghost endpoints included;
         the library drops them).  weight: int32 edge property per edge (WEIGHT_ABSENT where the edge
-        has none: Fulgora only fails if a message crosses such an edge), or None."""
+        has none: Fulgora only fails if a message crosses such an edge), or None.
+        float_weights=True returns the weight column as float64 instead (each value through float(), NaN
+        where the edge has none): what Graph.set_weights_f64 takes for a Double property."""
         vid = np.fromiter((v.id for v in self.vertices.values() if not v.ghost), dtype=np.int64)
         src = np.fromiter((e.out_id for e in self.edges), dtype=np.int64, count=len(self.edges))
         dst = np.fromiter((e.in_id for e in self.edges), dtype=np.int64, count=len(self.edges))
         weight = None
-        if weight_property is not None:
+        if weight_property is not None and float_weights:
+            weight = np.fromiter((float(e.properties[weight_property]) if weight_property in e.properties
+                                  else float("nan") for e in self.edges), dtype=np.float64, count=len(self.edges))
+        elif weight_property is not None:
             from ._lib import WEIGHT_ABSENT
             w = [int(e.properties[weight_property]) if weight_property in e.properties else int(WEIGHT_ABSENT)
                  for e in self.edges]

@@ -150,8 +150,8 @@ class ShortestPathVertexProgram(VertexProgram):
     """Depth on the GPU (Fulgora forces {Local(bothE), Global}), paths rebuilt on the host.
 
     TinkerPop's two further knobs [TP-recall]: distanceProperty(key) makes a path's length the sum of that edge
-    property (Integer, >= 1 here: anything else is refused with ProgramNotSupported at submit), and maxDistance
-    then bounds that sum, inclusive; edgeDirection("out" | "in" | "both") restricts the edges a path follows
+    property (Integer >= 1, or Double: finite and > 0, summed in IEEE binary64 with exact ties only; anything
+    else is refused with ProgramNotSupported at submit), and maxDistance then bounds that sum, inclusive; edgeDirection("out" | "in" | "both") restricts the edges a path follows
     (default "both").  memory.getIteration() is 1 + the number of edges of the longest returned path (1 when
     there is none), with or without a distance property: this project's rule, not pinned by any reference
     test.
@@ -192,7 +192,9 @@ class ShortestPathVertexProgram(VertexProgram):
             return self
 
         def maxDistance(self, d):  # noqa: N802
-            self.configuration["maxDistance"] = int(d)
+            # a non-integral bound is kept (the sums of a Double distanceProperty); the hop route and the integer
+            # weights' route apply int() to it
+            self.configuration["maxDistance"] = int(d) if float(d).is_integer() else float(d)
             return self
 
         def includeEdges(self, include):  # noqa: N802

@@ -17,7 +17,17 @@ JG_ADJ_OUT; direction IN (the adjacency jg_shortest_distance relaxes).
                       the smallest weight of the u -> v edges (a host dictionary of the edge list, built outside
                       the timed part), --host-reps times;
       the vertex sets and (sampled) predecessor lists of the two routes are compared.
-Usage: python tools/weighted_paths_bench.py [--scale 20] [--runs 5] [--reps 5] [--host-reps 1] [--wmax 255]
+--f64: the double-weight route beside the integer one, in one process (one JSON line): the same graph over BOTH and
+over IN, weights 1..wmax as int32 and as the same values in doubles (jg_graph_set_weights_f64) on one graph.
+  keep    `runs` calls each of jg_sssp_keep and jg_sssp_keep_f64, interleaved, after one warm call each;
+  dags    jg_sssp_kept_dag and jg_sssp_kept_dag_f64 to 1000 random reached targets and to every reached vertex,
+          `reps` builds each after one warm-up (HIP-event compute_ms, the library's byte model);
+  checks  the two planes are equal (integer-valued doubles below 2^53 add exactly) and so are the two DAGs'
+          predecessor lists, vertex by vertex.
+  Byte model of a keep: every entry of the relaxed adjacency read once (4 B column, 4 or 8 B weight, an 8 B
+  distance probe) and 32 B per row (the distance's init, the kept plane, a queue entry with its edge offset); the
+  re-relaxed rows and the atomics are not counted, so it is a floor.
+Usage: python tools/weighted_paths_bench.py [--scale 20] [--runs 5] [--reps 5] [--host-reps 1] [--wmax 255] [--f64]
 """
 import argparse
 import json
@@ -114,6 +124,84 @@ def cell(g, ctx, jg, n, target, reps, host_reps, minw):
     return out
 
 
+def lists_by_vertex(dag):
+    """(per-vertex predecessor counts, the predecessors concatenated) in vertex order: the DAG without the order
+    of its equal distances."""
+    vertex, _, off, pred = dag
+    perm = np.argsort(vertex, kind="stable")
+    cnt = np.diff(off)[perm]
+    start = np.repeat(off[:-1][perm] - np.r_[0, np.cumsum(cnt)[:-1]], cnt)
+    return vertex[perm], cnt, pred[start + np.arange(int(cnt.sum()))]
+
+
+def f64_mode(a, jg, n, s, t, w, vid, seed):
+    E = jg._lib
+    ctx = jg.Context((0,))
+    line = {"workload": f"f64_paths_rmat{a.scale}_ef{a.ef}_w1-{a.wmax}", "n": n, "m": len(s), "seed_row": seed,
+            "runs": a.runs, "reps": a.reps}
+    wf = w.astype(np.float64)
+    for name, direction in (("both", jg.DIR_BOTH), ("in", jg.DIR_IN)):
+        both = direction == jg.DIR_BOTH
+        g = ctx.build(vid, vid[s], vid[t], weight=w,
+                      flags=((jg.ADJ_BOTH | E.ADJ_WEIGHT_BOTH) if both else (jg.ADJ_IN | jg.ADJ_OUT)) | E.ADJ_EDGE_INDEX)
+        g.set_weights_f64(wf)
+        entries = int(g.info()["num_edges"]) * (2 if both else 1)
+        g.sssp_keep(vid[seed], direction)
+        g.sssp_keep_f64(vid[seed], direction)
+        ms = {"int": [], "f64": []}
+        passes = {}
+        for _ in range(a.runs):
+            for kind, keep in (("int", g.sssp_keep), ("f64", g.sssp_keep_f64)):
+                keep(vid[seed], direction)
+                st = ctx.stats()
+                ms[kind].append(st["compute_ms"])
+                passes[kind] = int(st["levels"])
+        out = {"entries": entries}
+        for kind, wbytes in (("int", 4), ("f64", 8)):
+            b = entries * (12.0 + wbytes) + 32.0 * n
+            c = med(ms[kind])
+            out["keep_" + kind] = {"ms": [round(x, 4) for x in ms[kind]], "ms_median": c, "ms_range": rng_of(ms[kind]),
+                                   "passes": passes[kind], "model_bytes": b,
+                                   "frac_of_8TBs": round(b / (c * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+        out["keep_f64_over_int"] = round(med(ms["f64"]) / med(ms["int"]), 3)
+        out["keep_model_ratio"] = round((entries * 20.0 + 32.0 * n) / (entries * 16.0 + 32.0 * n), 3)
+        g.sssp_keep(vid[seed], direction)
+        row_i = g.sssp_kept_row()
+        reached = (row_i != jg.DIST_ABSENT) & (row_i > 0)
+        some = np.zeros(n, bool)
+        some[np.random.default_rng(a.scale).choice(np.flatnonzero(reached), 1000, replace=False)] = True
+        dags = {}
+        for kind in ("int", "f64"):
+            if kind == "f64":
+                g.sssp_keep_f64(vid[seed], direction)
+                row_f = g.sssp_kept_row_f64()
+                out["planes_equal"] = bool(np.array_equal(
+                    row_f, np.where(row_i == jg.DIST_ABSENT, np.inf, row_i.astype(np.float64))))
+            build = g.sssp_kept_dag_build if kind == "int" else g.sssp_kept_dag_f64_build
+            for cname, target in (("targets_1000", some), ("target_none", None)):
+                comp = []
+                for rep_ in range(a.reps + 1):
+                    nv, ne, _ = build(target)
+                    st = ctx.stats()
+                    if rep_:
+                        comp.append(st["compute_ms"])
+                c = med(comp)
+                out[f"dag_{kind}_{cname}"] = {
+                    "dag_vertices": int(nv), "dag_entries": int(ne), "rounds": int(st["levels"]),
+                    "row_entries_walked": int(st["edges_traversed"]), "compute_ms": c, "compute_ms_range": rng_of(comp),
+                    "model_bytes": st["algorithmic_bytes"],
+                    "frac_of_8TBs": round(st["algorithmic_bytes"] / (c * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+                dags[kind, cname] = lists_by_vertex((g.sssp_kept_dag if kind == "int" else g.sssp_kept_dag_f64)(target))
+        for cname in ("targets_1000", "target_none"):
+            out["dags_equal_" + cname] = bool(all(np.array_equal(x, y) for x, y in zip(dags["int", cname], dags["f64", cname])))
+            out[f"dag_f64_over_int_{cname}"] = round(out[f"dag_f64_{cname}"]["compute_ms"] / out[f"dag_int_{cname}"]["compute_ms"], 3)
+        assert out["planes_equal"] and out["dags_equal_targets_1000"] and out["dags_equal_target_none"], out
+        line[name] = out
+        g.close()
+    print(json.dumps(line), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=int, default=20)
@@ -123,6 +211,7 @@ def main():
     ap.add_argument("--host-reps", type=int, default=1)
     ap.add_argument("--wmax", type=int, default=255)
     ap.add_argument("--no-dag", action="store_true", help="part (a) only")
+    ap.add_argument("--f64", action="store_true", help="the double-weight route beside the integer one")
     a = ap.parse_args()
     import janusgraph_amd as jg
     from sd_bench import kronecker
@@ -131,6 +220,8 @@ def main():
     w = np.random.default_rng(a.scale).integers(1, a.wmax + 1, len(s)).astype(np.int32)
     vid = (np.arange(n, dtype=np.int64) + 1) << 8
     seed = int(np.bincount(t, minlength=n).argmax())
+    if a.f64:
+        return f64_mode(a, jg, n, s, t, w, vid, seed)
     ctx = jg.Context((0,))
     g = ctx.build(vid, vid[s], vid[t], weight=w, flags=jg.ADJ_IN | (0 if a.no_dag else jg.ADJ_OUT))
     line = {"workload": f"weighted_paths_rmat{a.scale}_ef{a.ef}_w1-{a.wmax}", "n": n, "m": len(s), "seed_row": seed,
