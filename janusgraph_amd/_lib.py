@@ -267,6 +267,13 @@ def tune_set(key: str, value: int):
     check(load().jg_tune_set(key.encode(), int(value)))
 
 
+def prim_probe(op: int, pattern: int, bits: int, n: int):
+    """tune_set("prim_probe", ...) (tests; csrc/jg_prim_probe.hip): one device primitive (op 0..8) on a generated
+    input of n elements (pattern; bits: the sorts' key width) against plain host code.  Raises JanusGpuError:
+    JG_ERR_STATE on a difference, JG_ERR_ARG on a bad argument."""
+    tune_set("prim_probe", int(op) | int(pattern) << 4 | int(bits) << 8 | int(n) << 16)
+
+
 def comm_unique_id() -> bytes:
     buf = ctypes.create_string_buffer(UNIQUE_ID_BYTES)
     check(load().jg_comm_unique_id(ctypes.cast(buf, ctypes.c_void_p)))

@@ -19,6 +19,7 @@
 #include "jg_cache.h"
 #include "jg_internal.h"
 #include "jg_labelset.h"
+#include "jg_prim.h"
 
 namespace jg {
 
@@ -687,6 +688,11 @@ int jg_tune_set(const char* key, int64_t value) {
     jg::Tune& t = jg::tune();
     if (k == "dev_poison_probe") {  // not a knob: checks that JG_DEV_POISON fills blocks (jg_common.h)
         jg::dev_poison_probe(value);
+        return JG_OK;
+    }
+    if (k == "prim_probe") {  // not a knob: one primitive of jg_prim.hip against host code (jg_prim_probe.hip)
+        jg::prim::prim_probe(value);
+        jg::dev_cache_sync();
         return JG_OK;
     }
     // int knobs: name, field, allowed range

@@ -93,5 +93,10 @@ int64_t compact_indices(const uint8_t* flags, int64_t n, int64_t* idx_out, hipSt
 int64_t compact_indices(const uint8_t* flags, int64_t n, int64_t* idx_out, DevBuf<int64_t>& pos,
                         DevBuf<int64_t>& scan, hipStream_t s);
 
+// jg_tune_set("prim_probe", op | pattern << 4 | bits << 8 | n << 16) (tests; jg_prim_probe.hip): runs one of the
+// primitives above on a generated input of n elements and fails (JG_ERR_STATE) unless the result equals plain
+// host code's, element for element.  A bad argument fails (JG_ERR_ARG) before the device is touched.
+void prim_probe(int64_t value);
+
 }  // namespace prim
 }  // namespace jg
