@@ -646,33 +646,80 @@ class Graph:
 
     DAG_READ_ENTRIES = 1 << 28  # predecessors per jg_bfs_kept_dag_read call (1 GiB of int32)
 
-    def bfs_kept_dag_build(self, s, target=None):
-        """jg_bfs_kept_dag: builds the predecessor DAG of kept row s on the device (target: one flag per
-        vertex, None = every reached vertex).  Returns (num_vertices, num_entries, deepest)."""
-        t = None
-        if target is not None:
-            t = np.ascontiguousarray(target, np.uint8)
-            if t.ndim != 1 or len(t) != self.n:
-                raise ValueError("target needs one flag per vertex")
-        nv, ne, deepest = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        check(load().jg_bfs_kept_dag(self._h, int(s), _ptr(t), ctypes.byref(nv), ctypes.byref(ne),
-                                     ctypes.byref(deepest)))
-        return nv.value, ne.value, deepest.value
+    def _target_mask(self, target):
+        """The DAG builders' target: None (every reached vertex) or one uint8 flag per vertex."""
+        if target is None:
+            return None
+        t = np.ascontiguousarray(target, np.uint8)
+        if t.ndim != 1 or len(t) != self.n:
+            raise ValueError("target needs one flag per vertex")
+        return t
 
-    def bfs_kept_dag_read(self, first, count, want_pred=True):
-        """jg_bfs_kept_dag_read of the held DAG's vertices [first, first + count): (vertex, depth, off, pred)
-        with ABSOLUTE offsets; pred = entries [off[0], off[-1]) (None unless want_pred)."""
+    def _dag_build(self, fn, top_type, *args):
+        """One of the DAG builders `fn` (its arguments before the outputs: args): (num_vertices, num_entries, top),
+        top the deepest depth / farthest distance, a top_type."""
+        nv, ne, top = ctypes.c_int64(0), ctypes.c_int64(0), top_type(0)
+        check(fn(self._h, *args, ctypes.byref(nv), ctypes.byref(ne), ctypes.byref(top)))
+        return nv.value, ne.value, top.value
+
+    def _dag_read(self, fn, value_dtype, first, count, want_pred):
+        """Vertices [first, first + count) of the held DAG that `fn` reads: (vertex, value, off, pred) with
+        ABSOLUTE offsets; pred = entries [off[0], off[-1]) (None unless want_pred)."""
         vertex = np.empty(max(count, 1), np.int32)
-        depth = np.empty(max(count, 1), np.int32)
+        value = np.empty(max(count, 1), value_dtype)
         off = np.empty(count + 1, np.int64)
-        check(load().jg_bfs_kept_dag_read(self._h, int(first), int(count), _ptr(vertex), _ptr(depth), _ptr(off), None))
+        check(fn(self._h, int(first), int(count), _ptr(vertex), _ptr(value), _ptr(off), None))
         pred = None
         if want_pred:
             k = int(off[-1] - off[0])
             pred = np.empty(max(k, 1), np.int32)
-            check(load().jg_bfs_kept_dag_read(self._h, int(first), int(count), None, None, None, _ptr(pred)))
+            check(fn(self._h, int(first), int(count), None, None, None, _ptr(pred)))
             pred = pred[:k]
-        return vertex[:count], depth[:count], off, pred
+        return vertex[:count], value[:count], off, pred
+
+    def _dag_read_edges(self, read_fn, read_edges_fn, first, count, entries):
+        """The edge ordinals of entries [off[first], off[first + count]) of the held edge-listing DAG that read_fn
+        and read_edges_fn read (`entries`: their number, when the caller knows it)."""
+        if entries is None:
+            off = np.empty(count + 1, np.int64)
+            check(read_fn(self._h, int(first), int(count), None, None, _ptr(off), None))
+            entries = int(off[-1] - off[0])
+        edge = np.empty(max(entries, 1), np.uint32)
+        check(read_edges_fn(self._h, int(first), int(count), _ptr(edge)))
+        return edge[:entries]
+
+    def _dag_whole(self, read, read_edges, raw_read_fn, nv, ne):
+        """(vertex, value, off, pred) of a held DAG of nv vertices and ne entries, and its edge ordinals after them
+        when read_edges is not None.  read / read_edges: the family's public readers, raw_read_fn: the library's.
+        More than DAG_READ_ENTRIES entries are read in vertex ranges of at most that many (a vertex with more is
+        read alone), each range straight into its place."""
+        if ne <= self.DAG_READ_ENTRIES:
+            whole = read(0, nv)
+            return whole if read_edges is None else whole + (read_edges(0, nv, ne),)
+        vertex, value, off, _ = read(0, nv, want_pred=False)
+        pred = np.empty(ne, np.int32)
+        edge = None if read_edges is None else np.empty(ne, np.uint32)
+        first = 0
+        while first < nv:
+            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
+            last = min(max(last, first + 1), nv)
+            b, e = int(off[first]), int(off[last])
+            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * b)
+            check(raw_read_fn(self._h, first, last - first, None, None, None, into))
+            if edge is not None:
+                edge[b:e] = read_edges(first, last - first, e - b)
+            first = last
+        return (vertex, value, off, pred) if edge is None else (vertex, value, off, pred, edge)
+
+    def bfs_kept_dag_build(self, s, target=None):
+        """jg_bfs_kept_dag: builds the predecessor DAG of kept row s on the device (target: one flag per
+        vertex, None = every reached vertex).  Returns (num_vertices, num_entries, deepest)."""
+        return self._dag_build(load().jg_bfs_kept_dag, ctypes.c_int32, int(s), _ptr(self._target_mask(target)))
+
+    def bfs_kept_dag_read(self, first, count, want_pred=True):
+        """jg_bfs_kept_dag_read of the held DAG's vertices [first, first + count): (vertex, depth, off, pred)
+        with ABSOLUTE offsets; pred = entries [off[0], off[-1]) (None unless want_pred)."""
+        return self._dag_read(load().jg_bfs_kept_dag_read, np.int32, first, count, want_pred)
 
     def bfs_kept_dag(self, s, target=None):
         """The predecessor DAG of kept row s (bfs_keep): (vertex, depth, off, pred).  vertex[j] (output-order
@@ -680,93 +727,43 @@ class Graph:
         pred[off[j]:off[j + 1]] in jg_graph_neighbors order.  Built on the device (jg_bfs_kept_dag), read in
         vertex ranges of at most DAG_READ_ENTRIES predecessors (a vertex with more is read alone)."""
         nv, ne, _ = self.bfs_kept_dag_build(s, target)
-        if ne <= self.DAG_READ_ENTRIES:
-            return self.bfs_kept_dag_read(0, nv)
-        vertex, depth, off, _ = self.bfs_kept_dag_read(0, nv, want_pred=False)
-        pred = np.empty(ne, np.int32)
-        first = 0
-        while first < nv:
-            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
-            last = min(max(last, first + 1), nv)
-            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * int(off[first]))
-            check(load().jg_bfs_kept_dag_read(self._h, first, last - first, None, None, None, into))
-            first = last
-        return vertex, depth, off, pred
-
-    def _dag_edge_ranges(self, read, read_edges, nv, ne):
-        """(vertex, value, off, pred, edge) of a held edge-listing DAG, its entries read in vertex ranges of at
-        most DAG_READ_ENTRIES (a vertex with more is read alone); read / read_edges: the family's readers."""
-        vertex, value, off, _ = read(0, nv, want_pred=False)
-        pred = np.empty(ne, np.int32)
-        edge = np.empty(ne, np.uint32)
-        first = 0
-        while first < nv:
-            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
-            last = min(max(last, first + 1), nv)
-            b, e = int(off[first]), int(off[last])
-            pred[b:e] = read(first, last - first)[3]
-            edge[b:e] = read_edges(first, last - first, e - b)
-            first = last
-        return vertex, value, off, pred, edge
+        return self._dag_whole(self.bfs_kept_dag_read, None, load().jg_bfs_kept_dag_read, nv, ne)
 
     def bfs_kept_dag_edges_build(self, s, target=None):
         """jg_bfs_kept_dag_edges: as bfs_kept_dag_build, for the edge-listing DAG (one entry per qualifying
         adjacency entry; the graph needs ADJ_EDGE_INDEX).  It replaces a held bfs_kept_dag DAG."""
-        t = None
-        if target is not None:
-            t = np.ascontiguousarray(target, np.uint8)
-            if t.ndim != 1 or len(t) != self.n:
-                raise ValueError("target needs one flag per vertex")
-        nv, ne, deepest = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        check(load().jg_bfs_kept_dag_edges(self._h, int(s), _ptr(t), ctypes.byref(nv), ctypes.byref(ne),
-                                           ctypes.byref(deepest)))
-        return nv.value, ne.value, deepest.value
+        return self._dag_build(load().jg_bfs_kept_dag_edges, ctypes.c_int32, int(s), _ptr(self._target_mask(target)))
 
     def bfs_kept_dag_read_edges(self, first, count, entries=None):
         """jg_bfs_kept_dag_read_edges: the edge ordinals of the held edge-listing DAG's entries
         [off[first], off[first + count]) (`entries`: their number, when the caller knows it)."""
-        if entries is None:
-            off = np.empty(count + 1, np.int64)
-            check(load().jg_bfs_kept_dag_read(self._h, int(first), int(count), None, None, _ptr(off), None))
-            entries = int(off[-1] - off[0])
-        edge = np.empty(max(entries, 1), np.uint32)
-        check(load().jg_bfs_kept_dag_read_edges(self._h, int(first), int(count), _ptr(edge)))
-        return edge[:entries]
+        return self._dag_read_edges(load().jg_bfs_kept_dag_read, load().jg_bfs_kept_dag_read_edges, first, count,
+                                    entries)
 
     def bfs_kept_dag_edges(self, s, target=None):
         """The edge-listing predecessor DAG of kept row s: (vertex, depth, off, pred, edge).  vertex, depth and
         their order are bfs_kept_dag's; pred[off[j]:off[j + 1]] lists one predecessor per qualifying entry of
         vertex[j]'s reverse row, in row order (parallel edges repeat it), edge[...] that entry's edge ordinal."""
         nv, ne, _ = self.bfs_kept_dag_edges_build(s, target)
-        return self._dag_edge_ranges(self.bfs_kept_dag_read, self.bfs_kept_dag_read_edges, nv, ne)
+        return self._dag_whole(self.bfs_kept_dag_read, self.bfs_kept_dag_read_edges, load().jg_bfs_kept_dag_read,
+                               nv, ne)
 
     def sssp_kept_dag_edges_build(self, target=None, max_distance=-1):
         """jg_sssp_kept_dag_edges: as sssp_kept_dag_build, for the edge-listing DAG (one entry per tight
         adjacency entry; the graph needs ADJ_EDGE_INDEX).  It replaces a held sssp_kept_dag DAG."""
-        t = None
-        if target is not None:
-            t = np.ascontiguousarray(target, np.uint8)
-            if t.ndim != 1 or len(t) != self.n:
-                raise ValueError("target needs one flag per vertex")
-        nv, ne, far = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        check(load().jg_sssp_kept_dag_edges(self._h, _ptr(t), int(max_distance), ctypes.byref(nv), ctypes.byref(ne),
-                                            ctypes.byref(far)))
-        return nv.value, ne.value, far.value
+        return self._dag_build(load().jg_sssp_kept_dag_edges, ctypes.c_int64, _ptr(self._target_mask(target)),
+                               int(max_distance))
 
     def sssp_kept_dag_read_edges(self, first, count, entries=None):
         """jg_sssp_kept_dag_read_edges, as bfs_kept_dag_read_edges."""
-        if entries is None:
-            off = np.empty(count + 1, np.int64)
-            check(load().jg_sssp_kept_dag_read(self._h, int(first), int(count), None, None, _ptr(off), None))
-            entries = int(off[-1] - off[0])
-        edge = np.empty(max(entries, 1), np.uint32)
-        check(load().jg_sssp_kept_dag_read_edges(self._h, int(first), int(count), _ptr(edge)))
-        return edge[:entries]
+        return self._dag_read_edges(load().jg_sssp_kept_dag_read, load().jg_sssp_kept_dag_read_edges, first, count,
+                                    entries)
 
     def sssp_kept_dag_edges(self, target=None, max_distance=-1):
         """The edge-listing twin of sssp_kept_dag: (vertex, dist, off, pred, edge), as bfs_kept_dag_edges."""
         nv, ne, _ = self.sssp_kept_dag_edges_build(target, max_distance)
-        return self._dag_edge_ranges(self.sssp_kept_dag_read, self.sssp_kept_dag_read_edges, nv, ne)
+        return self._dag_whole(self.sssp_kept_dag_read, self.sssp_kept_dag_read_edges, load().jg_sssp_kept_dag_read,
+                               nv, ne)
 
     def sssp_keep(self, source, direction=DIR_BOTH):
         """jg_sssp_keep: the smallest summed weights from `source` along `direction` (weights >= 1; DIR_BOTH
@@ -789,30 +786,13 @@ class Graph:
         """jg_sssp_kept_dag: builds the tight-edge predecessor DAG of the kept distances on the device (target:
         one flag per vertex, None = every reached vertex; max_distance < 0: no bound).  Returns
         (num_vertices, num_entries, farthest)."""
-        t = None
-        if target is not None:
-            t = np.ascontiguousarray(target, np.uint8)
-            if t.ndim != 1 or len(t) != self.n:
-                raise ValueError("target needs one flag per vertex")
-        nv, ne, far = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        check(load().jg_sssp_kept_dag(self._h, _ptr(t), int(max_distance), ctypes.byref(nv), ctypes.byref(ne),
-                                      ctypes.byref(far)))
-        return nv.value, ne.value, far.value
+        return self._dag_build(load().jg_sssp_kept_dag, ctypes.c_int64, _ptr(self._target_mask(target)),
+                               int(max_distance))
 
     def sssp_kept_dag_read(self, first, count, want_pred=True):
         """jg_sssp_kept_dag_read of the held DAG's vertices [first, first + count): (vertex, dist, off, pred)
         with ABSOLUTE offsets; pred = entries [off[0], off[-1]) (None unless want_pred)."""
-        vertex = np.empty(max(count, 1), np.int32)
-        dist = np.empty(max(count, 1), np.int64)
-        off = np.empty(count + 1, np.int64)
-        check(load().jg_sssp_kept_dag_read(self._h, int(first), int(count), _ptr(vertex), _ptr(dist), _ptr(off), None))
-        pred = None
-        if want_pred:
-            k = int(off[-1] - off[0])
-            pred = np.empty(max(k, 1), np.int32)
-            check(load().jg_sssp_kept_dag_read(self._h, int(first), int(count), None, None, None, _ptr(pred)))
-            pred = pred[:k]
-        return vertex[:count], dist[:count], off, pred
+        return self._dag_read(load().jg_sssp_kept_dag_read, np.int64, first, count, want_pred)
 
     def sssp_kept_dag(self, target=None, max_distance=-1):
         """The minimum-weight-path predecessor DAG of the kept distances (sssp_keep): (vertex, dist, off, pred).
@@ -820,18 +800,7 @@ class Graph:
         predecessors pred[off[j]:off[j + 1]] in jg_graph_neighbors order of the reverse direction.  Built on
         the device (jg_sssp_kept_dag), read in vertex ranges as bfs_kept_dag."""
         nv, ne, _ = self.sssp_kept_dag_build(target, max_distance)
-        if ne <= self.DAG_READ_ENTRIES:
-            return self.sssp_kept_dag_read(0, nv)
-        vertex, dist, off, _ = self.sssp_kept_dag_read(0, nv, want_pred=False)
-        pred = np.empty(ne, np.int32)
-        first = 0
-        while first < nv:
-            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
-            last = min(max(last, first + 1), nv)
-            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * int(off[first]))
-            check(load().jg_sssp_kept_dag_read(self._h, first, last - first, None, None, None, into))
-            first = last
-        return vertex, dist, off, pred
+        return self._dag_whole(self.sssp_kept_dag_read, None, load().jg_sssp_kept_dag_read, nv, ne)
 
     # ---- the same over double weights (jg_graph_set_weights_f64): distances are float64, +inf = unreached ----
 
@@ -858,15 +827,8 @@ class Graph:
         return row
 
     def _sssp_kept_dag_f64_call(self, fn, target, max_distance):
-        t = None
-        if target is not None:
-            t = np.ascontiguousarray(target, np.uint8)
-            if t.ndim != 1 or len(t) != self.n:
-                raise ValueError("target needs one flag per vertex")
-        nv, ne, far = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0)
         md = -1.0 if max_distance is None else float(max_distance)
-        check(fn(self._h, _ptr(t), md, ctypes.byref(nv), ctypes.byref(ne), ctypes.byref(far)))
-        return nv.value, ne.value, far.value
+        return self._dag_build(fn, ctypes.c_double, _ptr(self._target_mask(target)), md)
 
     def sssp_kept_dag_f64_build(self, target=None, max_distance=-1.0):
         """jg_sssp_kept_dag_f64: as sssp_kept_dag_build over a plane of sssp_keep_f64 (max_distance: a float,
@@ -880,39 +842,19 @@ class Graph:
 
     def sssp_kept_dag_f64_read(self, first, count, want_pred=True):
         """jg_sssp_kept_dag_read_f64, as sssp_kept_dag_read with float64 distances."""
-        vertex = np.empty(max(count, 1), np.int32)
-        dist = np.empty(max(count, 1), np.float64)
-        off = np.empty(count + 1, np.int64)
-        check(load().jg_sssp_kept_dag_read_f64(self._h, int(first), int(count), _ptr(vertex), _ptr(dist), _ptr(off), None))
-        pred = None
-        if want_pred:
-            k = int(off[-1] - off[0])
-            pred = np.empty(max(k, 1), np.int32)
-            check(load().jg_sssp_kept_dag_read_f64(self._h, int(first), int(count), None, None, None, _ptr(pred)))
-            pred = pred[:k]
-        return vertex[:count], dist[:count], off, pred
+        return self._dag_read(load().jg_sssp_kept_dag_read_f64, np.float64, first, count, want_pred)
 
     def sssp_kept_dag_f64(self, target=None, max_distance=-1.0):
         """The minimum-weight-path predecessor DAG of the kept float64 distances (sssp_keep_f64): (vertex, dist,
         off, pred) as sssp_kept_dag, an edge u -> v tight iff fl(dist[u] + w) == dist[v] exactly."""
         nv, ne, _ = self.sssp_kept_dag_f64_build(target, max_distance)
-        if ne <= self.DAG_READ_ENTRIES:
-            return self.sssp_kept_dag_f64_read(0, nv)
-        vertex, dist, off, _ = self.sssp_kept_dag_f64_read(0, nv, want_pred=False)
-        pred = np.empty(ne, np.int32)
-        first = 0
-        while first < nv:
-            last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
-            last = min(max(last, first + 1), nv)
-            into = ctypes.c_void_p(pred.ctypes.data + pred.itemsize * int(off[first]))
-            check(load().jg_sssp_kept_dag_read_f64(self._h, first, last - first, None, None, None, into))
-            first = last
-        return vertex, dist, off, pred
+        return self._dag_whole(self.sssp_kept_dag_f64_read, None, load().jg_sssp_kept_dag_read_f64, nv, ne)
 
     def sssp_kept_dag_edges_f64(self, target=None, max_distance=-1.0):
         """The edge-listing twin of sssp_kept_dag_f64: (vertex, dist, off, pred, edge)."""
         nv, ne, _ = self.sssp_kept_dag_edges_f64_build(target, max_distance)
-        return self._dag_edge_ranges(self.sssp_kept_dag_f64_read, self.sssp_kept_dag_read_edges, nv, ne)
+        return self._dag_whole(self.sssp_kept_dag_f64_read, self.sssp_kept_dag_read_edges,
+                               load().jg_sssp_kept_dag_read_f64, nv, ne)
 
     def neighbors(self, rows, direction=DIR_BOTH):
         """jg_graph_neighbors: (off, nbr) CSR of the given output-order rows, in output-order indices."""

@@ -335,12 +335,7 @@ class GpuGraphComputer:
         direction = _PATH_DIRECTIONS[vp.edge_direction]
         reverse = _REVERSE_DIRECTION[direction]
         vid, src, dst, _ = self.graph.snapshot()
-        index = {int(v): i for i, v in enumerate(vid.tolist())}
-        sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
-        target = None
-        if vp.targets is not None:
-            target = np.zeros(len(vid), bool)
-            target[[index[t] for t in vp.targets if t in index]] = True
+        sources, target = _path_endpoints(vp, vid)
         both = direction == _lib.DIR_BOTH
         flags = _lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT
         if vp.include_edges:
@@ -404,12 +399,7 @@ class GpuGraphComputer:
                 f"ShortestPathVertexProgram with distanceProperty {vp.distance_property!r} is not run by "
                 f"GpuGraphComputer: " + (f"{missing} edge(s) lack the property" if missing else
                                          "an edge has a weight < 1") + "; delegate to FulgoraGraphComputer")
-        index = {int(v): i for i, v in enumerate(vid.tolist())}
-        sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
-        target = None
-        if vp.targets is not None:
-            target = np.zeros(len(vid), bool)
-            target[[index[t] for t in vp.targets if t in index]] = True
+        sources, target = _path_endpoints(vp, vid)
         both = direction == _lib.DIR_BOTH
         g = ctx.build(vid, src, dst, w, flags=(_lib.ADJ_BOTH | _lib.ADJ_WEIGHT_BOTH) if both
                       else _lib.ADJ_IN | _lib.ADJ_OUT)
@@ -455,12 +445,7 @@ class GpuGraphComputer:
         vid, src, dst, w = self.graph.snapshot(weight_property=key, float_weights=True)
         if len(w) and not (np.isfinite(w).all() and w.min() > 0):
             raise refuse("a weight is not finite and > 0")
-        index = {int(v): i for i, v in enumerate(vid.tolist())}
-        sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
-        target = None
-        if vp.targets is not None:
-            target = np.zeros(len(vid), bool)
-            target[[index[t] for t in vp.targets if t in index]] = True
+        sources, target = _path_endpoints(vp, vid)
         both = direction == _lib.DIR_BOTH
         try:
             g = ctx.build(vid, src, dst, flags=(_lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT) | _lib.ADJ_EDGE_INDEX)
@@ -497,6 +482,18 @@ class GpuGraphComputer:
                     v.properties.update(kv)
             return self.graph
         return ComputedGraph(self.graph, props)
+
+
+def _path_endpoints(vp, vid):
+    """ShortestPathVertexProgram's sources as snapshot indices (every vertex when none are given; unknown ids are
+    skipped) and its targets as one flag per vertex (None: every vertex)."""
+    index = {int(v): i for i, v in enumerate(vid.tolist())}
+    sources = [index[s] for s in (vp.sources if vp.sources is not None else vid.tolist()) if s in index]
+    target = None
+    if vp.targets is not None:
+        target = np.zeros(len(vid), bool)
+        target[[index[t] for t in vp.targets if t in index]] = True
+    return sources, target
 
 
 def _int_bound(d):

@@ -215,6 +215,16 @@ struct VecPos {
     __device__ __forceinline__ int64_t operator()(int64_t row) const { return base + row; }
 };
 
+template <class V>  // a held predecessor DAG (jg_pathdag.hip; one shard only: shard 0's member holds it)
+struct HeldDag {
+    DevBuf<int32_t> vertex, pred;  // [nv] caller-order vertices by descending value; [ne] their predecessors
+    DevBuf<V> value;               // [nv] depths, or 8-byte distances
+    DevBuf<int64_t> off;           // [nv + 1] offsets into pred
+    DevBuf<uint32_t> edge;         // [ne] an edge-listing DAG's ordinals, parallel to pred (edges)
+    int64_t nv = -1, ne = 0;       // nv -1: none held
+    bool edges = false;            // it lists edges (the *_edges entry points): one entry per qualifying entry
+};
+
 struct Shard {
     int device = 0;
     int index = 0;           // shard id r in [0, P)
@@ -269,20 +279,13 @@ struct Shard {
     int sd_hist[4] = {0, 0, 0, 0};  // delta-stepping: steps of the last calls (the first batch's size)
     int sd_hist_n = 0;
     DevBuf<int32_t> kept_depth;              // [kept_nsrc][rows] jg_bfs_keep's depth planes (jg_bfs_kept_row)
-    // the predecessor DAG of one kept row (jg_bfs_kept_dag, jg_pathdag.hip; Graph::dag_nv vertices, depth
-    // descending): caller-order vertex and depth, offsets into dag_pred, caller-order predecessors
-    DevBuf<int32_t> dag_vertex, dag_depth, dag_pred;
-    DevBuf<int64_t> dag_off;                 // [dag_nv + 1]
-    DevBuf<uint32_t> dag_edge;               // an edge-listing DAG's ordinals, parallel to dag_pred (Graph::dag_edges)
+    HeldDag<int32_t> dag;                    // the predecessor DAG of one kept row (jg_bfs_kept_dag)
     // jg_sssp_keep's distance plane ([rows] int64, local row order, LLONG_MIN: absent) and the tight-edge
-    // predecessor DAG of it (jg_sssp_kept_dag; Graph::wdag_nv vertices, distance descending): buffers of
-    // their own, so that a kept BFS row and its DAG can be held at the same time.  jg_sssp_keep_f64's plane and
-    // DAG take the same slots (Graph::sssp_f64, Graph::wdag_f64): the bit patterns of non-negative doubles,
-    // whose signed integer order is the distance order; +Inf's pattern: absent
+    // predecessor DAG of it (jg_sssp_kept_dag): a holding of its own, so that a kept BFS row and its DAG can be
+    // held at the same time.  jg_sssp_keep_f64's plane and DAG take the same slots (Graph::sssp_f64,
+    // Graph::wdag_f64): the patterns of doubles >= 0, whose integer order is the distance order; +Inf's: absent
     DevBuf<long long> sssp_dist;
-    DevBuf<int32_t> wdag_vertex, wdag_pred;
-    DevBuf<int64_t> wdag_dist, wdag_off;     // [wdag_nv], [wdag_nv + 1]
-    DevBuf<uint32_t> wdag_edge;              // as dag_edge (Graph::wdag_edges)
+    HeldDag<long long> wdag;
     // the held component census (jg_cc_census, jg_census.hip; Graph::census_listed pairs, population
     // descending): the component's vertex id and its population.  Its own buffers, not program scratch.
     DevBuf<int64_t> census_vid, census_pop;
@@ -330,20 +333,16 @@ struct Graph {
     // each rank on the first shard's device, its host copy made on first use (sharded CC output)
     int kept_nsrc = 0;  // depth rows kept by jg_bfs_keep
     int kept_dir = 0;   // the direction of that traversal (jg_bfs_kept_dag reads the reverse adjacency)
-    int64_t dag_nv = -1, dag_ne = 0;  // the held predecessor DAG (Shard::dag_*); -1: none
-    bool dag_edges = false;           // it lists edges (jg_bfs_kept_dag_edges): one entry per qualifying adjacency entry
     bool sssp_kept = false;           // jg_sssp_keep's plane is held (Shard::sssp_dist)
     int sssp_dir = 0;                 // its direction (jg_sssp_kept_dag reads the reverse adjacency)
     bool sssp_f64 = false;            // the held plane is jg_sssp_keep_f64's (bit patterns of doubles)
-    bool wdag_f64 = false;            // the held weighted DAG was built from such a plane
+    bool wdag_f64 = false;            // the held weighted DAG (Shard::wdag) was built from such a plane
     // JG_ADJ_EDGE_INDEX: the length of the caller's edge list (what Csr::eidx indexes); -1 without the flag
     int64_t edge_list_m = -1;
     // jg_graph_set_weights_f64: the double weights are set (Csr::wf beside every built adjacency), and their
     // smallest, largest and mean value (a fixed-order reduction: the same bits on every run)
     bool has_wf = false;
     double wf_min = 0, wf_max = 0, wf_mean = 0;
-    int64_t wdag_nv = -1, wdag_ne = 0;  // the held weighted predecessor DAG (Shard::wdag_*); -1: none
-    bool wdag_edges = false;            // it lists edges (jg_sssp_kept_dag_edges)
     int64_t census_listed = -1;       // the held component census (Shard::census_*); -1: none
     // the held PageRank top list (jg_pagerank_top, jg_top.hip; top_listed records in the list's order): the
     // caller-order index, rank and edgeCount of each, merged from the shards' selects and held on the host

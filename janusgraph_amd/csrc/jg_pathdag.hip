@@ -26,6 +26,10 @@
 // device") shares the emit: the count and fill passes are templates over the DAG's flavour (HopDag: depth
 // planes and "one level up"; TightDag: distance planes and "a tight edge"), which names the per-vertex value
 // and decides whether an entry counts.  Its sweep runs by rounds instead of levels (wdag_round_kernel).
+// On the host the two drivers (bfs_kept_dag_t, sssp_kept_dag_t) hold what differs: their checks, seed, sweep,
+// what their stats mean and their byte model.  The rest is one copy: the common checks, the target upload and
+// the timed region (dag_only_shard, DagRun), the emit (dag_emit<T>, into the shard's HeldDag of the family), the
+// readers (dag_read, dag_read_edges) and the drop (drop_held).
 //
 // The edge-listing DAGs (jg_bfs_kept_dag_edges, jg_sssp_kept_dag_edges; DESIGN.md, "Edge-listing predecessor
 // DAG") are the same sweeps with two more flavours (HopEdgeDag, TightEdgeDag): the predicate without the
@@ -534,86 +538,173 @@ const Csr& reverse_csr(const Shard& sh, int dir) {
     return dir == JG_DIR_BOTH ? sh.both : dir == JG_DIR_OUT ? sh.in : sh.out;
 }
 
-}  // namespace
-
-void bfs_kept_dag_drop(Graph& g) {
+template <class V>
+void drop_held(Graph& g, HeldDag<V> Shard::*held) {
     for (auto& sp : g.shards) {
         DeviceGuard dg(*sp);
-        sp->dag_vertex.reset();
-        sp->dag_depth.reset();
-        sp->dag_pred.reset();
-        sp->dag_off.reset();
-        sp->dag_edge.reset();
+        (*sp).*held = HeldDag<V>{};
     }
-    g.dag_nv = -1;
-    g.dag_ne = 0;
-    g.dag_edges = false;
 }
+
+// The checks every flavour makes before its family's own (`name`: the entry point, for the messages)
+Shard& dag_only_shard(Graph& g, const std::string& name, bool edges, const char* sharded_hint = "") {
+    if (edges && !(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, name + "_edges: the graph was built without JG_ADJ_EDGE_INDEX");
+    if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, name + " runs on one shard" + sharded_hint);
+    return *g.shards[0];
+}
+
+// One run of either driver, begun after the family's checks: the remaining checks (`counters`: what the rows must
+// fit, for the message), then the family's held DAG goes (`drop`) and the call's stats start empty.  start() and
+// stop() bound the timed region: the target mask travels before it, stop() leaves its length in compute_ms.
+// `on`: one byte per row, zeroed by start(), set by the seed (the targets) and the sweep (the DAG's other rows);
+// compact() lists the rows whose byte is set, in row order, in idx, and returns their number.
+struct DagRun {
+    Shard& sh;
+    jg_stats& last;
+    DeviceGuard dg;
+    hipStream_t st;
+    int64_t rows;
+    DevBuf<uint8_t> dtarget;
+    Event t0, t1;
+    DevBuf<uint32_t> on;  // the bytes as words (the sweeps set a byte with an atomic OR on its word)
+    DevBuf<int64_t> idx, cpos, cscan;
+    DagRun(Graph& g, Shard& shard, const std::string& name, const char* counters, void (*drop)(Graph&))
+        : sh(shard), last(g.ctx->last), dg(sh), st(sh.stream), rows(sh.rows) {
+        if (sh.rows != g.n || sh.dense_rows.size() < (size_t)std::max<int64_t>(sh.rows, 1))
+            fail(JG_ERR_UNSUPPORTED, name + ": the shard does not hold every vertex");
+        if (sh.rows >> (64 - kPackShift))
+            fail(JG_ERR_UNSUPPORTED, name + ": too many rows for the " + counters + " counters");
+        drop(g);
+        last = jg_stats{};
+    }
+    void start(const uint8_t* target) {
+        if (target) {  // one flag per vertex: the shard holds them all
+            dtarget.alloc((size_t)rows);
+            copy_h2d(dtarget.get(), target, (size_t)rows, st);
+        }
+        JG_HIP(hipEventRecord(t0, st));
+        on.alloc((size_t)((rows + 3) / 4));
+        JG_HIP(hipMemsetAsync(on.get(), 0, on.bytes(), st));
+    }
+    uint8_t* on8() const { return reinterpret_cast<uint8_t*>(on.get()); }
+    int64_t compact() {
+        if (!idx.size()) idx.alloc((size_t)rows);
+        return prim::compact_indices(on8(), rows, idx.get(), cpos, cscan, st);
+    }
+    void stop() {
+        JG_HIP(hipEventRecord(t1, st));
+        JG_HIP(hipEventSynchronize(t1));
+        float ms = 0;
+        JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+        last.compute_ms = ms;
+    }
+};
+
+// The emit of every flavour T, after the sweep left the DAG rows' `on` bytes set: the held DAG's buffers, from the
+// plane `dep` whose largest value among the targets is `top` (dbits: its width).  nv, ne: the DAG's vertices and
+// listed entries; mf: the entries its rows hold.
+struct DagEmitted {
+    int64_t nv, ne, mf, launches;
+};
+template <class T>
+DagEmitted dag_emit(DagRun& run, const Csr& c, const typename T::Val* dep, typename T::Val top, int dbits,
+                    typename T::Extra extra, HeldDag<typename T::Val>& held) {
+    using V = typename T::Val;
+    const Shard& sh = run.sh;
+    hipStream_t st = run.st;
+    int64_t launches = 0;
+    const int64_t nv = run.compact();
+    const DevBuf<int64_t>& idx = run.idx;
+    DevBuf<uint64_t> vkey((size_t)nv);
+    DevBuf<uint32_t> vval((size_t)nv);
+    dag_keys_kernel<V><<<grid_for(nv), kBlock, 0, st>>>(idx.get(), nv, dep, top, vkey.get(), vval.get());
+    JG_LAUNCH_CHECK();
+    prim::radix_sort(vkey.get(), vval.get(), nv, dbits, st);
+    DevBuf<int32_t> local((size_t)nv);
+    DevBuf<int64_t> len((size_t)nv), qoff((size_t)nv + 1);
+    held.vertex.alloc((size_t)nv);
+    held.value.alloc((size_t)nv);
+    held.off.alloc((size_t)nv + 1);
+    dag_unpack_kernel<V><<<grid_for(nv), kBlock, 0, st>>>(vkey.get(), vval.get(), nv, top, c.row_ptr.get(),
+                                                          sh.dense_rows.get(), local.get(), held.vertex.get(),
+                                                          held.value.get(), len.get());
+    JG_LAUNCH_CHECK();
+    prim::exclusive_scan(len.get(), qoff.get(), nv, st);
+    int64_t mf = 0;
+    copy_d2h(&mf, qoff.get() + nv, sizeof(int64_t), st);
+    DevBuf<int32_t> cnt((size_t)nv);
+    JG_HIP(hipMemsetAsync(cnt.get(), 0, cnt.bytes(), st));
+    const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
+    const size_t nr = (size_t)std::max<int64_t>(nranges, 1);
+    DevBuf<int32_t> rfi(nr), rli(nr), rca(nr), rcl(nr);
+    DagWalk<T> wk{extra, local.get(), held.value.get(), qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(), dep,
+                  sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr, nullptr,
+                  T::kEdges ? c.eidx.get() : nullptr, nullptr};
+    const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
+    if (mf > 0) {
+        dag_count_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
+        JG_LAUNCH_CHECK();
+        ++launches;
+    }
+    prim::exclusive_scan(cnt.get(), held.off.get(), nv, st);
+    int64_t ne = 0;
+    copy_d2h(&ne, held.off.get() + nv, sizeof(int64_t), st);
+    held.pred.alloc((size_t)std::max<int64_t>(ne, 1));
+    if (T::kEdges) held.edge.alloc((size_t)std::max<int64_t>(ne, 1));
+    if (mf > 0) {
+        wk.off = held.off.get();
+        wk.pred = held.pred.get();
+        wk.edge = held.edge.get();
+        dag_fill_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
+        JG_LAUNCH_CHECK();
+        ++launches;
+    }
+    return {nv, ne, mf, launches};
+}
+
+}  // namespace
+
+void bfs_kept_dag_drop(Graph& g) { drop_held(g, &Shard::dag); }
 
 // T: HopDag (jg_bfs_kept_dag) or HopEdgeDag (jg_bfs_kept_dag_edges).  Seed, sweep and the DAG's vertices do not
 // depend on T; the count and fill passes do.
 template <class T>
 static void bfs_kept_dag_t(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64_t* ne_out,
                            int32_t* deepest_out) {
-    if (T::kEdges && !(g.flags & JG_ADJ_EDGE_INDEX))
-        fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag_edges: the graph was built without JG_ADJ_EDGE_INDEX");
-    if (g.P != 1 || g.shards.size() != 1)
-        fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag runs on one shard (sharded graphs: walk back on the host)");
+    Shard& sh = dag_only_shard(g, "jg_bfs_kept_dag", T::kEdges, " (sharded graphs: walk back on the host)");
     if (s < 0 || s >= g.kept_nsrc) fail(JG_ERR_ARG, "no kept depth row with that index (jg_bfs_keep)");
-    Shard& sh = *g.shards[0];
     const Csr& c = reverse_csr(sh, g.kept_dir);
     if (!c.present())
         fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag reads the reverse of the kept traversal's adjacency: not built");
-    if (sh.rows != g.n || sh.dense_rows.size() < (size_t)std::max<int64_t>(sh.rows, 1))
-        fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag: the shard does not hold every vertex");
-    if (sh.rows >> (64 - kPackShift)) fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag: too many rows for the level counters");
-    bfs_kept_dag_drop(g);
-    Ctx& ctx = *g.ctx;
-    ctx.last = jg_stats{};
-    DeviceGuard dg(sh);
-    hipStream_t st = sh.stream;
-    const int64_t rows = sh.rows;
+    DagRun run(g, sh, "jg_bfs_kept_dag", "level", bfs_kept_dag_drop);
+    hipStream_t st = run.st;
+    const int64_t rows = run.rows;
     const int32_t* dep = sh.kept_depth.get() + (int64_t)s * rows;
     const auto finish = [&](int64_t nv, int64_t ne, int32_t deepest) {
-        g.dag_nv = nv;
-        g.dag_ne = ne;
-        g.dag_edges = T::kEdges;
+        sh.dag.nv = nv;
+        sh.dag.ne = ne;
+        sh.dag.edges = T::kEdges;
         if (nv_out) *nv_out = nv;
         if (ne_out) *ne_out = ne;
         if (deepest_out) *deepest_out = deepest;
-        ctx.last.levels = deepest;
-        ctx.last.supersteps = deepest < 0 ? 0 : deepest;
+        run.last.levels = deepest;
+        run.last.supersteps = deepest < 0 ? 0 : deepest;
     };
     if (rows == 0) return finish(0, 0, -1);
-
-    DevBuf<uint8_t> dtarget;
-    if (target) {  // the mask travels before the timed region
-        dtarget.alloc((size_t)g.n);
-        copy_h2d(dtarget.get(), target, (size_t)g.n, st);
-    }
-    Event t0, t1;
-    JG_HIP(hipEventRecord(t0, st));
+    run.start(target);
 
     // ---- seed ----
-    const int64_t on_words = (rows + 3) / 4;
-    DevBuf<uint32_t> on((size_t)on_words);
     DevBuf<int32_t> d_deepest(1);
-    JG_HIP(hipMemsetAsync(on.get(), 0, on.bytes(), st));
     JG_HIP(hipMemsetAsync(d_deepest.get(), 0xff, sizeof(int32_t), st));
-    uint8_t* on8 = reinterpret_cast<uint8_t*>(on.get());
-    dag_seed_kernel<<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(dep, sh.dense_rows.get(), dtarget.get(), rows, on8,
-                                                                    d_deepest.get());
+    dag_seed_kernel<<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(dep, sh.dense_rows.get(), run.dtarget.get(), rows,
+                                                                    run.on8(), d_deepest.get());
     JG_LAUNCH_CHECK();
-    DevBuf<int64_t> idx((size_t)rows), cpos, cscan;
-    const int64_t nt = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
+    const int64_t nt = run.compact();
     if (nt == 0) {
-        JG_HIP(hipEventRecord(t1, st));
-        JG_HIP(hipEventSynchronize(t1));
-        float ms = 0;
-        JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+        run.stop();
         finish(0, 0, -1);
-        ctx.last.compute_ms = ms;
-        ctx.last.algorithmic_bytes = 10.0 * (double)rows;
+        run.last.algorithmic_bytes = 10.0 * (double)rows;
         return;
     }
     int32_t deepest = -1;
@@ -621,7 +712,7 @@ static void bfs_kept_dag_t(Graph& g, int s, const uint8_t* target, int64_t* nv_o
     const int dbits = std::max(bits_for((uint64_t)deepest), 1);
     DevBuf<uint64_t> tkey((size_t)nt);
     DevBuf<uint32_t> tval((size_t)nt);
-    dag_keys_kernel<int32_t><<<grid_for(nt), kBlock, 0, st>>>(idx.get(), nt, dep, deepest, tkey.get(), tval.get());
+    dag_keys_kernel<int32_t><<<grid_for(nt), kBlock, 0, st>>>(run.idx.get(), nt, dep, deepest, tkey.get(), tval.get());
     JG_LAUNCH_CHECK();
     prim::radix_sort(tkey.get(), tval.get(), nt, dbits, st);
 
@@ -632,7 +723,7 @@ static void bfs_kept_dag_t(Graph& g, int s, const uint8_t* target, int64_t* nv_o
     DevBuf<int64_t> lbase((size_t)deepest + 2);
     JG_HIP(hipMemsetAsync(packed.get(), 0, packed.bytes(), st));
     JG_HIP(hipMemsetAsync(lbase.get(), 0, lbase.bytes(), st));
-    DagStep sp{c.row_ptr.get(), c.col.get(), dep, on.get(), vq.get(), qo.get(), packed.get(), lbase.get(),
+    DagStep sp{c.row_ptr.get(), c.col.get(), dep, run.on.get(), vq.get(), qo.get(), packed.get(), lbase.get(),
                tkey.get(), tval.get(), nt, 0, deepest};
     const unsigned step_grid = grid_for(std::max<int64_t>(c.nnz / 4, rows), kBlock, 1024);
     for (int32_t d = deepest + 1; d >= 1; --d) {
@@ -640,62 +731,12 @@ static void bfs_kept_dag_t(Graph& g, int s, const uint8_t* target, int64_t* nv_o
         dag_step_kernel<<<step_grid, kBlock, 0, st>>>(sp);
         JG_LAUNCH_CHECK();
     }
-    int64_t launches = (int64_t)deepest + 1;
 
-    // ---- emit ----
-    const int64_t nv = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
-    DevBuf<uint64_t> vkey((size_t)nv);
-    DevBuf<uint32_t> vval((size_t)nv);
-    dag_keys_kernel<int32_t><<<grid_for(nv), kBlock, 0, st>>>(idx.get(), nv, dep, deepest, vkey.get(), vval.get());
-    JG_LAUNCH_CHECK();
-    prim::radix_sort(vkey.get(), vval.get(), nv, dbits, st);
-    DevBuf<int32_t> local((size_t)nv);
-    DevBuf<int64_t> len((size_t)nv), qoff((size_t)nv + 1);
-    sh.dag_vertex.alloc((size_t)nv);
-    sh.dag_depth.alloc((size_t)nv);
-    sh.dag_off.alloc((size_t)nv + 1);
-    dag_unpack_kernel<int32_t><<<grid_for(nv), kBlock, 0, st>>>(vkey.get(), vval.get(), nv, deepest, c.row_ptr.get(),
-                                                                sh.dense_rows.get(), local.get(), sh.dag_vertex.get(),
-                                                                sh.dag_depth.get(), len.get());
-    JG_LAUNCH_CHECK();
-    prim::exclusive_scan(len.get(), qoff.get(), nv, st);
-    int64_t mf = 0;
-    copy_d2h(&mf, qoff.get() + nv, sizeof(int64_t), st);
-    DevBuf<int32_t> cnt((size_t)nv);
-    JG_HIP(hipMemsetAsync(cnt.get(), 0, cnt.bytes(), st));
-    const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
-    DevBuf<int32_t> rfi((size_t)std::max<int64_t>(nranges, 1)), rli((size_t)std::max<int64_t>(nranges, 1)),
-        rca((size_t)std::max<int64_t>(nranges, 1)), rcl((size_t)std::max<int64_t>(nranges, 1));
-    DagWalk<T> wk{{}, local.get(), sh.dag_depth.get(), qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(), dep,
-                  sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr, nullptr,
-                  T::kEdges ? c.eidx.get() : nullptr, nullptr};
-    const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
-    if (mf > 0) {
-        dag_count_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
-        JG_LAUNCH_CHECK();
-        ++launches;
-    }
-    prim::exclusive_scan(cnt.get(), sh.dag_off.get(), nv, st);
-    int64_t ne = 0;
-    copy_d2h(&ne, sh.dag_off.get() + nv, sizeof(int64_t), st);
-    sh.dag_pred.alloc((size_t)std::max<int64_t>(ne, 1));
-    if (T::kEdges) sh.dag_edge.alloc((size_t)std::max<int64_t>(ne, 1));
-    if (mf > 0) {
-        wk.off = sh.dag_off.get();
-        wk.pred = sh.dag_pred.get();
-        wk.edge = sh.dag_edge.get();
-        dag_fill_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
-        JG_LAUNCH_CHECK();
-        ++launches;
-    }
-    JG_HIP(hipEventRecord(t1, st));
-    JG_HIP(hipEventSynchronize(t1));
-    float ms = 0;
-    JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    const auto [nv, ne, mf, emit_launches] = dag_emit<T>(run, c, dep, deepest, dbits, {}, sh.dag);
+    run.stop();
     finish(nv, ne, deepest);
-    ctx.last.compute_ms = ms;
-    ctx.last.kernel_launches = launches;
-    ctx.last.edges_traversed = (double)mf;
+    run.last.kernel_launches = (int64_t)deepest + 1 + emit_launches;
+    run.last.edges_traversed = (double)mf;
     // Byte model.  Seed and the two compactions: 10 B per row (depth, dense index, mask and `on` byte), 9 B
     // per row per compaction (flag + position).  Each of the three walks (sweep, count, fill) reads a
     // DAG-row entry's column and probes its depth: 3 x 8 B per entry.  A DAG vertex costs ~64 B (two
@@ -703,7 +744,7 @@ static void bfs_kept_dag_t(Graph& g, int s, const uint8_t* target, int64_t* nv_o
     // emitted predecessor 8 B (dense probe + store).  The edge-listing DAG adds the ordinal: 4 B per walked
     // entry in the fill pass (the listed entries' ordinals, fetched by the line) and 4 B per emitted entry (its
     // store); the count pass reads no ordinal.
-    ctx.last.algorithmic_bytes = 28.0 * (double)rows + 24.0 * (double)mf + 64.0 * (double)nv + 8.0 * (double)ne +
+    run.last.algorithmic_bytes = 28.0 * (double)rows + 24.0 * (double)mf + 64.0 * (double)nv + 8.0 * (double)ne +
                                  (T::kEdges ? 4.0 * (double)mf + 4.0 * (double)ne : 0.0);
 }
 
@@ -713,57 +754,62 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
     else bfs_kept_dag_t<HopDag>(g, s, target, nv_out, ne_out, deepest_out);
 }
 
-void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
-                       int64_t* off_out, int32_t* pred_out) {
-    if (g.dag_nv < 0) fail(JG_ERR_STATE, "no predecessor DAG is held (jg_bfs_kept_dag)");
-    if (first < 0 || count < 0 || first > g.dag_nv || count > g.dag_nv - first)
+// The two readers of a held DAG `h` of shard sh; the exported names check first that the right one is held.
+// Entries [off[first], off[first + count]) of `entries` (pred or edge):
+template <class E>
+static void dag_read_entries(const Shard& sh, const DevBuf<int64_t>& off, const DevBuf<E>& entries, int64_t first,
+                             int64_t count, E* out) {
+    int64_t b = 0, e = 0;
+    copy_d2h(&b, off.get() + first, sizeof(int64_t), sh.stream);
+    copy_d2h(&e, off.get() + first + count, sizeof(int64_t), sh.stream);
+    copy_d2h(out, entries.get() + b, (size_t)(e - b) * sizeof(E), sh.stream);
+}
+// vertices [first, first + count): value_out takes the values as the DAG holds them, sizeof(V) bytes each
+template <class V>
+static void dag_read(const Shard& sh, const HeldDag<V>& h, int64_t first, int64_t count, int32_t* vertex_out,
+                     void* value_out, int64_t* off_out, int32_t* pred_out) {
+    if (first < 0 || count < 0 || first > h.nv || count > h.nv - first)
         fail(JG_ERR_ARG, "range outside the DAG's vertices");
-    if (g.dag_nv == 0) {
+    if (h.nv == 0) {
         if (off_out) off_out[0] = 0;
         return;
     }
-    Shard& sh = *g.shards[0];
     DeviceGuard dg(sh);
     hipStream_t st = sh.stream;
-    if (vertex_out) copy_d2h(vertex_out, sh.dag_vertex.get() + first, (size_t)count * sizeof(int32_t), st);
-    if (depth_out) copy_d2h(depth_out, sh.dag_depth.get() + first, (size_t)count * sizeof(int32_t), st);
-    if (off_out) copy_d2h(off_out, sh.dag_off.get() + first, (size_t)(count + 1) * sizeof(int64_t), st);
-    if (pred_out) {
-        int64_t b = 0, e = 0;
-        copy_d2h(&b, sh.dag_off.get() + first, sizeof(int64_t), st);
-        copy_d2h(&e, sh.dag_off.get() + first + count, sizeof(int64_t), st);
-        copy_d2h(pred_out, sh.dag_pred.get() + b, (size_t)(e - b) * sizeof(int32_t), st);
-    }
+    if (vertex_out) copy_d2h(vertex_out, h.vertex.get() + first, (size_t)count * sizeof(int32_t), st);
+    if (value_out) copy_d2h(value_out, h.value.get() + first, (size_t)count * sizeof(V), st);
+    if (off_out) copy_d2h(off_out, h.off.get() + first, (size_t)(count + 1) * sizeof(int64_t), st);
+    if (pred_out) dag_read_entries(sh, h.off, h.pred, first, count, pred_out);
+}
+// name: the entry point; built_by: the call that would have built an edge-listing DAG of this family
+template <class V>
+static void dag_read_edges(const Graph& g, const HeldDag<V>& h, const std::string& name, const std::string& built_by,
+                           int64_t first, int64_t count, uint32_t* edge_out) {
+    if (!(g.flags & JG_ADJ_EDGE_INDEX))
+        fail(JG_ERR_UNSUPPORTED, name + ": the graph was built without JG_ADJ_EDGE_INDEX");
+    if (h.nv < 0 || !h.edges) fail(JG_ERR_STATE, "no edge-listing " + built_by);
+    if (first < 0 || count < 0 || first > h.nv || count > h.nv - first)
+        fail(JG_ERR_ARG, "range outside the DAG's vertices");
+    if (h.nv == 0 || count == 0 || !edge_out) return;
+    const Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    dag_read_entries(sh, h.off, h.edge, first, count, edge_out);
+}
+
+void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
+                       int64_t* off_out, int32_t* pred_out) {
+    const Shard& sh = *g.shards[0];
+    if (sh.dag.nv < 0) fail(JG_ERR_STATE, "no predecessor DAG is held (jg_bfs_kept_dag)");
+    dag_read(sh, sh.dag, first, count, vertex_out, depth_out, off_out, pred_out);
 }
 
 void bfs_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {
-    if (!(g.flags & JG_ADJ_EDGE_INDEX))
-        fail(JG_ERR_UNSUPPORTED, "jg_bfs_kept_dag_read_edges: the graph was built without JG_ADJ_EDGE_INDEX");
-    if (g.dag_nv < 0 || !g.dag_edges) fail(JG_ERR_STATE, "no edge-listing predecessor DAG is held (jg_bfs_kept_dag_edges)");
-    if (first < 0 || count < 0 || first > g.dag_nv || count > g.dag_nv - first)
-        fail(JG_ERR_ARG, "range outside the DAG's vertices");
-    if (g.dag_nv == 0 || count == 0 || !edge_out) return;
-    Shard& sh = *g.shards[0];
-    DeviceGuard dg(sh);
-    hipStream_t st = sh.stream;
-    int64_t b = 0, e = 0;
-    copy_d2h(&b, sh.dag_off.get() + first, sizeof(int64_t), st);
-    copy_d2h(&e, sh.dag_off.get() + first + count, sizeof(int64_t), st);
-    copy_d2h(edge_out, sh.dag_edge.get() + b, (size_t)(e - b) * sizeof(uint32_t), st);
+    dag_read_edges(g, g.shards[0]->dag, "jg_bfs_kept_dag_read_edges", "predecessor DAG is held (jg_bfs_kept_dag_edges)",
+                   first, count, edge_out);
 }
 
 void sssp_kept_dag_drop(Graph& g) {
-    for (auto& sp : g.shards) {
-        DeviceGuard dg(*sp);
-        sp->wdag_vertex.reset();
-        sp->wdag_dist.reset();
-        sp->wdag_pred.reset();
-        sp->wdag_off.reset();
-        sp->wdag_edge.reset();
-    }
-    g.wdag_nv = -1;
-    g.wdag_ne = 0;
-    g.wdag_edges = false;
+    drop_held(g, &Shard::wdag);
     g.wdag_f64 = false;
 }
 
@@ -775,69 +821,44 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
                             int64_t* farthest_out) {
     using A = typename T::Arith;
     constexpr bool kF64 = std::is_same<A, TightF64>::value;
-    if (T::kEdges && !(g.flags & JG_ADJ_EDGE_INDEX))
-        fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag_edges: the graph was built without JG_ADJ_EDGE_INDEX");
-    if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag runs on one shard");
+    Shard& sh = dag_only_shard(g, "jg_sssp_kept_dag", T::kEdges);
     if (!g.sssp_kept) fail(JG_ERR_STATE, "no distance plane is kept (jg_sssp_keep)");
     if (g.sssp_f64 != kF64)
         fail(JG_ERR_STATE, kF64 ? "the kept plane holds integers (jg_sssp_keep): use jg_sssp_kept_dag"
                                 : "the kept plane holds doubles (jg_sssp_keep_f64): use jg_sssp_kept_dag_f64");
-    Shard& sh = *g.shards[0];
     const Csr& c = reverse_csr(sh, g.sssp_dir);
     if (!c.present() || A::weight_count(c) == 0)
         fail(JG_ERR_UNSUPPORTED,
              "jg_sssp_kept_dag reads the reverse of the kept direction's adjacency: not built, or built without weights");
-    if (sh.rows != g.n || sh.dense_rows.size() < (size_t)std::max<int64_t>(sh.rows, 1))
-        fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag: the shard does not hold every vertex");
-    if (sh.rows >> (64 - kPackShift)) fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag: too many rows for the round counters");
-    sssp_kept_dag_drop(g);
-    Ctx& ctx = *g.ctx;
-    ctx.last = jg_stats{};
-    DeviceGuard dg(sh);
-    hipStream_t st = sh.stream;
-    const int64_t rows = sh.rows;
+    DagRun run(g, sh, "jg_sssp_kept_dag", "round", sssp_kept_dag_drop);
+    hipStream_t st = run.st;
+    const int64_t rows = run.rows;
     const long long* dist = sh.sssp_dist.get();
     const auto finish = [&](int64_t nv, int64_t ne, int64_t farthest, int64_t rounds) {
-        g.wdag_nv = nv;
-        g.wdag_ne = ne;
-        g.wdag_edges = T::kEdges;
+        sh.wdag.nv = nv;
+        sh.wdag.ne = ne;
+        sh.wdag.edges = T::kEdges;
         g.wdag_f64 = kF64;
         if (nv_out) *nv_out = nv;
         if (ne_out) *ne_out = ne;
         if (farthest_out) *farthest_out = farthest;
-        ctx.last.levels = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
-        ctx.last.supersteps = ctx.last.levels;
+        run.last.levels = (int32_t)std::min<int64_t>(rounds, INT32_MAX);
+        run.last.supersteps = run.last.levels;
     };
     if (rows == 0) return finish(0, 0, -1, 0);
-
-    DevBuf<uint8_t> dtarget;
-    if (target) {  // the mask travels before the timed region
-        dtarget.alloc((size_t)g.n);
-        copy_h2d(dtarget.get(), target, (size_t)g.n, st);
-    }
-    Event t0, t1;
-    JG_HIP(hipEventRecord(t0, st));
+    run.start(target);
 
     // ---- seed ----
-    const int64_t on_words = (rows + 3) / 4;
-    DevBuf<uint32_t> on((size_t)on_words);
     DevBuf<long long> d_far(1);
-    JG_HIP(hipMemsetAsync(on.get(), 0, on.bytes(), st));
     JG_HIP(hipMemsetAsync(d_far.get(), 0xff, sizeof(long long), st));
-    uint8_t* on8 = reinterpret_cast<uint8_t*>(on.get());
-    wdag_seed_kernel<A::kAbsent><<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(dist, sh.dense_rows.get(), dtarget.get(), rows,
-                                                                     (long long)max_distance, on8, d_far.get());
+    wdag_seed_kernel<A::kAbsent><<<grid_for(rows, kBlock, 2048), kBlock, 0, st>>>(
+        dist, sh.dense_rows.get(), run.dtarget.get(), rows, (long long)max_distance, run.on8(), d_far.get());
     JG_LAUNCH_CHECK();
-    DevBuf<int64_t> idx((size_t)rows), cpos, cscan;
-    const int64_t nt = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
+    const int64_t nt = run.compact();
     if (nt == 0) {
-        JG_HIP(hipEventRecord(t1, st));
-        JG_HIP(hipEventSynchronize(t1));
-        float ms = 0;
-        JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+        run.stop();
         finish(0, 0, -1, 0);
-        ctx.last.compute_ms = ms;
-        ctx.last.algorithmic_bytes = 14.0 * (double)rows;
+        run.last.algorithmic_bytes = 14.0 * (double)rows;
         return;
     }
     long long farthest = -1;
@@ -849,9 +870,9 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
     DevBuf<int64_t> qo((size_t)rows + 1), len((size_t)rows);
     DevBuf<unsigned long long> ring((size_t)kWdRing + 1);
     DevBuf<int64_t> lbase((size_t)kWdRing);
-    WdagRound<A> rd{c.row_ptr.get(), c.col.get(), A::weights(c), dist, on.get(), vq.get(), qo.get(), ring.get(),
+    WdagRound<A> rd{c.row_ptr.get(), c.col.get(), A::weights(c), dist, run.on.get(), vq.get(), qo.get(), ring.get(),
                  lbase.get(), ring.get() + kWdRing, 0};
-    wdag_queue0_kernel<<<grid_for(nt), kBlock, 0, st>>>(idx.get(), nt, c.row_ptr.get(), vq.get(), len.get());
+    wdag_queue0_kernel<<<grid_for(nt), kBlock, 0, st>>>(run.idx.get(), nt, c.row_ptr.get(), vq.get(), len.get());
     JG_LAUNCH_CHECK();
     prim::exclusive_scan(len.get(), qo.get(), nt, st);
     wdag_ring0_kernel<A><<<1, kWave, 0, st>>>(rd, nt);
@@ -869,66 +890,15 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
         copy_d2h(&pk, ring.get() + r % kWdRing, sizeof pk, st);
         if ((pk & kEdgeMask) == 0) break;
     }
-    int64_t launches = r;
     unsigned long long rounds = 0;  // rounds whose queue had rows: the launched ones', and a last edgeless queue
     copy_d2h(&rounds, ring.get() + kWdRing, sizeof rounds, st);
     if ((pk >> kPackShift) > 0) ++rounds;
 
-    // ---- emit (the passes of the hop DAG, with the tight-edge predicate) ----
-    const int64_t nv = prim::compact_indices(on8, rows, idx.get(), cpos, cscan, st);
-    DevBuf<uint64_t> vkey((size_t)nv);
-    DevBuf<uint32_t> vval((size_t)nv);
-    dag_keys_kernel<long long><<<grid_for(nv), kBlock, 0, st>>>(idx.get(), nv, dist, farthest, vkey.get(), vval.get());
-    JG_LAUNCH_CHECK();
-    prim::radix_sort(vkey.get(), vval.get(), nv, dbits, st);
-    DevBuf<int32_t> local((size_t)nv);
-    DevBuf<int64_t> rlen((size_t)nv), qoff((size_t)nv + 1);
-    sh.wdag_vertex.alloc((size_t)nv);
-    sh.wdag_dist.alloc((size_t)nv);
-    sh.wdag_off.alloc((size_t)nv + 1);
-    long long* wd = reinterpret_cast<long long*>(sh.wdag_dist.get());
-    dag_unpack_kernel<long long><<<grid_for(nv), kBlock, 0, st>>>(vkey.get(), vval.get(), nv, farthest, c.row_ptr.get(),
-                                                                  sh.dense_rows.get(), local.get(),
-                                                                  sh.wdag_vertex.get(), wd, rlen.get());
-    JG_LAUNCH_CHECK();
-    prim::exclusive_scan(rlen.get(), qoff.get(), nv, st);
-    int64_t mf = 0;
-    copy_d2h(&mf, qoff.get() + nv, sizeof(int64_t), st);
-    DevBuf<int32_t> cnt((size_t)nv);
-    JG_HIP(hipMemsetAsync(cnt.get(), 0, cnt.bytes(), st));
-    const int64_t nranges = (mf + kDagRange - 1) / kDagRange;
-    const size_t nr = (size_t)std::max<int64_t>(nranges, 1);
-    DevBuf<int32_t> rfi(nr), rli(nr), rca(nr), rcl(nr);
-    DagWalk<T> wk{{A::weights(c)}, local.get(), wd, qoff.get(), nv, mf, nranges, c.row_ptr.get(), c.col.get(),
-                  dist, sh.dense_rows.get(), cnt.get(), rfi.get(), rli.get(), rca.get(), rcl.get(), nullptr,
-                  nullptr, T::kEdges ? c.eidx.get() : nullptr, nullptr};
-    const unsigned walk_grid = grid_for(nranges, kBlock / kWave, 16384);
-    if (mf > 0) {
-        dag_count_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
-        JG_LAUNCH_CHECK();
-        ++launches;
-    }
-    prim::exclusive_scan(cnt.get(), sh.wdag_off.get(), nv, st);
-    int64_t ne = 0;
-    copy_d2h(&ne, sh.wdag_off.get() + nv, sizeof(int64_t), st);
-    sh.wdag_pred.alloc((size_t)std::max<int64_t>(ne, 1));
-    if (T::kEdges) sh.wdag_edge.alloc((size_t)std::max<int64_t>(ne, 1));
-    if (mf > 0) {
-        wk.off = sh.wdag_off.get();
-        wk.pred = sh.wdag_pred.get();
-        wk.edge = sh.wdag_edge.get();
-        dag_fill_kernel<T><<<walk_grid, kBlock, 0, st>>>(wk);
-        JG_LAUNCH_CHECK();
-        ++launches;
-    }
-    JG_HIP(hipEventRecord(t1, st));
-    JG_HIP(hipEventSynchronize(t1));
-    float ms = 0;
-    JG_HIP(hipEventElapsedTime(&ms, t0, t1));
+    const auto [nv, ne, mf, emit_launches] = dag_emit<T>(run, c, dist, farthest, dbits, {A::weights(c)}, sh.wdag);
+    run.stop();
     finish(nv, ne, farthest, (int64_t)rounds);
-    ctx.last.compute_ms = ms;
-    ctx.last.kernel_launches = launches;
-    ctx.last.edges_traversed = (double)mf;
+    run.last.kernel_launches = (int64_t)r + emit_launches;
+    run.last.edges_traversed = (double)mf;
     // Byte model, as the hop DAG's with 8-byte distances and the weights.  Seed and the two compactions: 14 B
     // per row (distance, dense index, mask and `on` byte), 9 B per row per compaction (flag + position).  Each
     // of the three walks (sweep, count, fill) reads a DAG-row entry's column (4 B) and weight (4 B) and probes
@@ -938,7 +908,7 @@ static void sssp_kept_dag_t(Graph& g, const uint8_t* target, int64_t max_distanc
     // distance and the other outputs), an emitted predecessor 8 B (dense probe + store).  The edge-listing DAG
     // adds the ordinal as the hop DAG's does: 4 B per walked entry in the fill pass, 4 B per emitted entry.
     // The f64 flavours read an 8-byte weight: 3 x 20 B per entry.
-    ctx.last.algorithmic_bytes = 32.0 * (double)rows + (kF64 ? 60.0 : 48.0) * (double)mf + 72.0 * (double)nv +
+    run.last.algorithmic_bytes = 32.0 * (double)rows + (kF64 ? 60.0 : 48.0) * (double)mf + 72.0 * (double)nv +
                                  8.0 * (double)ne + (T::kEdges ? 4.0 * (double)mf + 4.0 * (double)ne : 0.0);
 }
 
@@ -968,58 +938,25 @@ void sssp_kept_dag_f64(Graph& g, const uint8_t* target, double max_distance, int
     }
 }
 
-// the read of either kind of weighted DAG (dist_out: the distances as the DAG holds them, 8 bytes each)
-static void wdag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out, int64_t* off_out,
-                      int32_t* pred_out) {
-    if (first < 0 || count < 0 || first > g.wdag_nv || count > g.wdag_nv - first)
-        fail(JG_ERR_ARG, "range outside the DAG's vertices");
-    if (g.wdag_nv == 0) {
-        if (off_out) off_out[0] = 0;
-        return;
-    }
-    Shard& sh = *g.shards[0];
-    DeviceGuard dg(sh);
-    hipStream_t st = sh.stream;
-    if (vertex_out) copy_d2h(vertex_out, sh.wdag_vertex.get() + first, (size_t)count * sizeof(int32_t), st);
-    if (dist_out) copy_d2h(dist_out, sh.wdag_dist.get() + first, (size_t)count * sizeof(int64_t), st);
-    if (off_out) copy_d2h(off_out, sh.wdag_off.get() + first, (size_t)(count + 1) * sizeof(int64_t), st);
-    if (pred_out) {
-        int64_t b = 0, e = 0;
-        copy_d2h(&b, sh.wdag_off.get() + first, sizeof(int64_t), st);
-        copy_d2h(&e, sh.wdag_off.get() + first + count, sizeof(int64_t), st);
-        copy_d2h(pred_out, sh.wdag_pred.get() + b, (size_t)(e - b) * sizeof(int32_t), st);
-    }
-}
-
 void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
                         int64_t* off_out, int32_t* pred_out) {
-    if (g.wdag_nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag)");
+    const Shard& sh = *g.shards[0];
+    if (sh.wdag.nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag)");
     if (g.wdag_f64) fail(JG_ERR_STATE, "the held weighted DAG has double distances: read it with jg_sssp_kept_dag_read_f64");
-    wdag_read(g, first, count, vertex_out, dist_out, off_out, pred_out);
+    dag_read(sh, sh.wdag, first, count, vertex_out, dist_out, off_out, pred_out);
 }
 
 void sssp_kept_dag_read_f64(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, double* dist_out,
                             int64_t* off_out, int32_t* pred_out) {
-    if (g.wdag_nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag_f64)");
+    const Shard& sh = *g.shards[0];
+    if (sh.wdag.nv < 0) fail(JG_ERR_STATE, "no weighted predecessor DAG is held (jg_sssp_kept_dag_f64)");
     if (!g.wdag_f64) fail(JG_ERR_STATE, "the held weighted DAG has integer distances: read it with jg_sssp_kept_dag_read");
-    wdag_read(g, first, count, vertex_out, reinterpret_cast<int64_t*>(dist_out), off_out, pred_out);
+    dag_read(sh, sh.wdag, first, count, vertex_out, dist_out, off_out, pred_out);
 }
 
 void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {
-    if (!(g.flags & JG_ADJ_EDGE_INDEX))
-        fail(JG_ERR_UNSUPPORTED, "jg_sssp_kept_dag_read_edges: the graph was built without JG_ADJ_EDGE_INDEX");
-    if (g.wdag_nv < 0 || !g.wdag_edges)
-        fail(JG_ERR_STATE, "no edge-listing weighted predecessor DAG is held (jg_sssp_kept_dag_edges)");
-    if (first < 0 || count < 0 || first > g.wdag_nv || count > g.wdag_nv - first)
-        fail(JG_ERR_ARG, "range outside the DAG's vertices");
-    if (g.wdag_nv == 0 || count == 0 || !edge_out) return;
-    Shard& sh = *g.shards[0];
-    DeviceGuard dg(sh);
-    hipStream_t st = sh.stream;
-    int64_t b = 0, e = 0;
-    copy_d2h(&b, sh.wdag_off.get() + first, sizeof(int64_t), st);
-    copy_d2h(&e, sh.wdag_off.get() + first + count, sizeof(int64_t), st);
-    copy_d2h(edge_out, sh.wdag_edge.get() + b, (size_t)(e - b) * sizeof(uint32_t), st);
+    dag_read_edges(g, g.shards[0]->wdag, "jg_sssp_kept_dag_read_edges",
+                   "weighted predecessor DAG is held (jg_sssp_kept_dag_edges)", first, count, edge_out);
 }
 
 }  // namespace jg

@@ -257,6 +257,42 @@ def test_random_multigraph(ctx, direction, kind):
     g.close()
 
 
+def test_ranged_read(ctx):
+    """Graph.sssp_kept_dag_f64 and sssp_kept_dag_edges_f64 read in ranges of DAG_READ_ENTRIES = 50 entries give,
+    array for array, what one read gives.  A hub with 60 tight predecessors, more than a range holds, is read
+    alone: 0 -> spoke -> hub over edges of the smallest weight, so no path reaches a spoke or the hub sooner."""
+    n, m, hub, fan = 200, 2000, 199, 60
+    rng = np.random.default_rng(11)
+    s, d = rng.integers(0, n, m), rng.integers(0, n, m)
+    w = random_weights("eighths", m, 3)
+    spokes = np.arange(1, fan + 1)
+    s[:fan], d[:fan] = 0, spokes
+    s[fan:2 * fan], d[fan:2 * fan] = spokes, hub
+    s[2 * fan:2 * fan + 10], d[2 * fan:2 * fan + 10] = spokes[:10], hub   # parallel: the edge DAG lists them too
+    w[:2 * fan + 10] = 0.125
+    dist, tight = weighted_dag(n, s, d, w.tolist(), DIR_OUT, 0)
+    dag_v, _ = model_dag(model_plane(dist), tight, None, -1.0)
+    entries = sum(len(tight[v]) for v in dag_v.tolist())
+    assert entries > 50 and len(tight[hub]) >= fan > 50 and hub in dag_v   # ranges, and a vertex read alone
+    g, vid = build(ctx, n, s, d, w, DIR_OUT)
+    try:
+        g.sssp_keep_f64(vid[0], DIR_OUT)
+        whole, whole_edges = g.sssp_kept_dag_f64(), g.sssp_kept_dag_edges_f64()
+        assert len(whole[3]) == entries and len(whole_edges[4]) >= entries + 10
+        g.DAG_READ_ENTRIES = 50
+        try:
+            ranged, ranged_edges = g.sssp_kept_dag_f64(), g.sssp_kept_dag_edges_f64()
+        finally:
+            del g.DAG_READ_ENTRIES
+        assert len(ranged) == 4 and len(ranged_edges) == 5
+        for a, b in zip(ranged + ranged_edges, whole + whole_edges):
+            assert a.dtype == b.dtype
+            np.testing.assert_array_equal(a.view(np.int64) if a.dtype == np.float64 else a,
+                                          b.view(np.int64) if b.dtype == np.float64 else b)
+    finally:
+        g.close()
+
+
 @pytest.fixture(scope="module")
 def rmat12(oracle_lib):
     from test_gpu_vdev import rmat_graph
