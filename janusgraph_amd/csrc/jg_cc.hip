@@ -1133,250 +1133,265 @@ __global__ __launch_bounds__(kBlock) void cc_rev_recv_kernel(const unsigned long
     add_fell(nchg, cnt);
 }
 
-// Every shard of the process (halo plans; cc_label holds the ranks).  false (labels untouched, message
-// vectors to be re-initialised) if the superstep count reaches the cap; else each shard's labels are
-// in cc_label.
-bool cc_union_find_sharded(Graph& g, int* iterations, int* rounds_out, double* work_bytes) {
-    const size_t ns = g.shards.size();
-    const int P = g.P;
-    struct St {
-        DevBuf<int32_t> tmin, label, rank, found, rbuf;
-        DevBuf<int64_t> send_off, woff;
-        DevBuf<unsigned long long> flag, sw;
-        DevBuf<unsigned long long> linked;  // [1] entries scanned by the second round (on the shard's device)
-        // sparse rounds: own rows whose label fell (this round's / the last round's), roots whose minimum
-        // fell, copies whose value fell; per-peer pair counts [2P] (forward, reverse) and cursors [P];
-        // the pair buffers and their per-peer offsets (pbase: send, roffd: receive)
-        DevBuf<unsigned long long> dirty[2], rootb, cb, pcnt, cursor, spairs, rpairs;
-        DevBuf<unsigned long long> nchg;  // [kFellLines * kFellStride] own rows whose label fell this round
-        DevBuf<int64_t> pbase, roffd;
-        int64_t ne = 0, len = 0, heavy = 0, nsend = 0;
-        int32_t giant = -1;
-        int giant_share = 0, all_found = 0;
-        SlotMap sm;
-    };
-    std::vector<St> st(ns);
-    const int kFirst = std::max(1, tune().cc_first);
-    double bytes = 0;
-    auto link_args = [&](size_t i) {
-        Shard& sh = *g.shards[i];
-        St& t = st[i];
-        return CcShardLink{sh.cc_msg[1].get(), sh.both.row_ptr.get(), sh.both.col.get(), sh.rows, t.ne, t.heavy, kFirst,
-                           t.flag.get(), t.found.get(), t.all_found, sh.halo_both.tbits};
-    };
-    // first round, giant sample, own flags, send-list flags
-    std::vector<uint64_t*> swv, flv;
-    for (size_t i = 0; i < ns; ++i) {
-        Shard& sh = *g.shards[i];
-        DeviceGuard dg(sh);
-        hipStream_t s = sh.stream;
-        St& t = st[i];
-        const Csr& c = sh.both;
-        const Halo& h = sh.halo_both;
-        t.ne = c.empty_from >= 0 ? std::min(c.empty_from, sh.rows) : sh.rows;
-        t.len = g.vec_len(sh, JG_ADJ_BOTH);
-        t.nsend = h.send_off[(size_t)P];
-        t.sm.ne = t.ne;
-        t.sm.cum[0] = 0;
-        for (int q = 0; q < P; ++q) {
-            const int64_t nr = q == sh.index ? 0 : h.recv_off[(size_t)q + 1] - h.recv_off[(size_t)q];
-            if (nr == 0) continue;
-            t.sm.start[t.sm.nseg] = (int64_t)h.seg_of(q, sh.index) << h.tbits;
-            t.sm.cum[t.sm.nseg + 1] = t.sm.cum[t.sm.nseg] + nr;
-            ++t.sm.nseg;
+bool cc_debug() {  // JG_DEBUG_CC: a line per label round and shard, and each shard's summary
+    static const bool on = std::getenv("JG_DEBUG_CC") != nullptr;
+    return on;
+}
+
+// The most frequent value of a sample (sorted here), and how often it occurs.
+int32_t most_frequent(std::vector<int32_t>& hs, int* share) {
+    std::sort(hs.begin(), hs.end());
+    int32_t val = -1;
+    *share = 0;
+    for (size_t a = 0, b = 0; a < hs.size(); a = b) {
+        while (b < hs.size() && hs[b] == hs[a]) ++b;
+        if ((int)(b - a) > *share) *share = (int)(b - a), val = hs[a];
+    }
+    return val;
+}
+
+// One local shard's state of the sharded union-find (CcShardedUf).
+struct CcUfShard {
+    Shard* sh = nullptr;
+    DevBuf<int32_t> tmin, label, rank, found, rbuf;
+    DevBuf<int64_t> send_off, woff;
+    DevBuf<unsigned long long> flag, sw, linked;  // linked: [1] entries scanned by the second round
+    // sparse rounds: own rows whose label fell (this round's / the last round's), roots whose minimum
+    // fell, copies whose value fell; per-peer pair counts [2P] (forward, reverse) and cursors [P];
+    // the pair buffers and their per-peer offsets (pbase: send, roffd: receive)
+    DevBuf<unsigned long long> dirty[2], rootb, cb, pcnt, cursor, spairs, rpairs;
+    DevBuf<unsigned long long> nchg;  // [kFellLines * kFellStride] own rows whose label fell this round
+    DevBuf<int64_t> pbase, roffd;
+    int64_t ne = 0, len = 0, heavy = 0, nsend = 0;
+    int32_t giant = -1;
+    int giant_share = 0, all_found = 0;
+    SlotMap sm;
+    int32_t* parent() const { return sh->cc_msg[1].get(); }
+};
+
+// Connected components of every shard of the process over the halo plans (cc_label holds the ranks): a union-find
+// per shard, tree labels over the halo until none falls, and one sharded BFS for the superstep count.  run() is false
+// (labels untouched, message vectors to be re-initialised) if that count reaches the cap; else the labels are in cc_label.
+class CcShardedUf {
+public:
+    explicit CcShardedUf(Graph& graph)
+        : g(graph), P(graph.P), kFirst(std::max(1, tune().cc_first)), sv(graph.shards.size()) {
+        for (size_t i = 0; i < sv.size(); ++i) sv[i].sh = &*g.shards[i];
+    }
+
+    bool run(int* iterations, double* work_bytes) {
+        first_round();
+        second_round();
+        label_rounds();
+        return finish(iterations, work_bytes);
+    }
+
+private:
+    template <class F>
+    void each(F&& f) {
+        for (CcUfShard& t : sv) {
+            DeviceGuard dg(*t.sh);
+            f(t, *t.sh);
         }
-        t.sm.total = t.ne + t.sm.cum[t.sm.nseg];
-        int32_t* parent = sh.cc_msg[1].get();
-        t.tmin.alloc(t.len);
-        t.label.alloc(std::max<int64_t>(sh.rows, 1));
-        t.rank.alloc(std::max<int64_t>(sh.rows, 1));
-        t.found.alloc(P);
-        t.rbuf.alloc(std::max<int64_t>(t.nsend, 1));
-        t.flag.alloc((t.len + 63) / 64);
-        const std::vector<int64_t> woff = halo_word_offsets(h, P);
-        t.sw.alloc(std::max<int64_t>(woff[(size_t)P], 1));
-        t.send_off.alloc(P + 1);
-        t.woff.alloc(P + 1);
-        copy_h2d(t.send_off.get(), h.send_off.data(), (P + 1) * sizeof(int64_t), s);
-        copy_h2d(t.woff.get(), woff.data(), (P + 1) * sizeof(int64_t), s);
-        JG_HIP(hipMemsetAsync(t.found.get(), 0, P * sizeof(int32_t), s));
-        JG_HIP(hipMemsetAsync(t.flag.get(), 0, t.flag.bytes(), s));
-        t.linked.alloc(1);
-        JG_HIP(hipMemsetAsync(t.linked.get(), 0, sizeof(unsigned long long), s));
-        if (sh.rows) {  // labels start at the ranks (cc_prepare_ranks)
-            JG_HIP(hipMemcpyAsync(t.label.get(), sh.cc_rank0.get(), sh.rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            JG_HIP(hipMemcpyAsync(t.rank.get(), sh.cc_rank0.get(), sh.rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        }
-        if (t.sm.total) {
-            cc_slots_init_kernel<<<grid_for(t.sm.total), kBlock, 0, s>>>(t.sm, parent);
-            JG_LAUNCH_CHECK();
-        }
-        if (t.ne > 0) {
-            DevBuf<int32_t> sample(1025);
-            uf_link_first_kernel<<<grid_for(t.ne), kBlock, 0, s>>>(parent, c.row_ptr.get(), c.col.get(),
-                                                                   c.first_col.get(), t.ne, kFirst);
-            JG_LAUNCH_CHECK();
-            cc_slots_compress_kernel<<<grid_for(t.sm.total), kBlock, 0, s>>>(t.sm, parent);
-            JG_LAUNCH_CHECK();
-            // the most frequent root among 1024 sampled own rows: the giant tree's
-            uf_sample_kernel<<<4, kBlock, 0, s>>>(parent, t.ne, 1024, sample.get());
-            JG_LAUNCH_CHECK();
-            heavy_rows_kernel<<<1, 1, 0, s>>>(c.row_ptr.get(), t.ne, sample.get() + 1024);
-            JG_LAUNCH_CHECK();
-            std::vector<int32_t> hs(1025);
-            copy_d2h(hs.data(), sample.get(), hs.size() * sizeof(int32_t), s);
-            t.heavy = hs[1024];
-            hs.pop_back();
-            std::sort(hs.begin(), hs.end());
-            size_t best = 0;
-            for (size_t a = 0; a < hs.size();) {
-                size_t b = a;
-                while (b < hs.size() && hs[b] == hs[a]) ++b;
-                if (b - a > best) {
-                    best = b - a;
-                    t.giant = hs[a];
-                    t.giant_share = (int)best;
-                }
-                a = b;
+    }
+
+    CcShardLink link_args(const CcUfShard& t) const {
+        return CcShardLink{t.parent(), t.sh->both.row_ptr.get(), t.sh->both.col.get(), t.sh->rows, t.ne, t.heavy, kFirst,
+                           t.flag.get(), t.found.get(), t.all_found, t.sh->halo_both.tbits};
+    }
+
+    // slot map and state, first links, giant sample, own flags, send-list flags
+    void first_round() {
+        each([&](CcUfShard& t, Shard& sh) {
+            hipStream_t s = sh.stream;
+            const Csr& c = sh.both;
+            const Halo& h = sh.halo_both;
+            t.ne = c.empty_from >= 0 ? std::min(c.empty_from, sh.rows) : sh.rows;
+            t.len = g.vec_len(sh, JG_ADJ_BOTH);
+            t.nsend = h.send_off[(size_t)P];
+            t.sm.ne = t.ne;
+            t.sm.cum[0] = 0;
+            for (int q = 0; q < P; ++q) {  // the slots: own rows with an edge, then each peer's copies
+                const int64_t nr = q == sh.index ? 0 : h.recv_off[(size_t)q + 1] - h.recv_off[(size_t)q];
+                if (nr == 0) continue;
+                t.sm.start[t.sm.nseg] = (int64_t)h.seg_of(q, sh.index) << h.tbits;
+                t.sm.cum[t.sm.nseg + 1] = t.sm.cum[t.sm.nseg] + nr;
+                ++t.sm.nseg;
             }
-            cc_own_flags_kernel<<<grid_for(((sh.rows + 63) / 64) * kWave), kBlock, 0, s>>>(parent, t.ne, sh.rows, t.giant,
-                                                                                          t.flag.get());
-            JG_LAUNCH_CHECK();
-        }
-        if (woff[(size_t)P] > 0) {
-            cc_pack_flags_kernel<<<grid_for(woff[(size_t)P] * kWave), kBlock, 0, s>>>(parent, t.giant, h.send_src.get(),
-                                                                              t.send_off.get(), t.woff.get(), P,
-                                                                              t.sw.get());
-            JG_LAUNCH_CHECK();
-        }
-        swv.push_back(reinterpret_cast<uint64_t*>(t.sw.get()));
-        flv.push_back(reinterpret_cast<uint64_t*>(t.flag.get()));
-    }
-    exchange_halo_bits(g, JG_ADJ_BOTH, swv, flv, false);  // the copies' flags: in their owner's giant tree
-    // the bounded search, then the second round
-    for (size_t i = 0; i < ns; ++i) {
-        Shard& sh = *g.shards[i];
-        DeviceGuard dg(sh);
-        hipStream_t s = sh.stream;
-        St& t = st[i];
-        if (t.ne == 0) continue;
-        if (tune().cc_uf_search) {  // 0: every peer takes the fallback (a parity-test variant)
-            cc_giant_search_kernel<<<(kCcSearchRows * kCcSearchSplit * kWave + kBlock - 1) / kBlock, kBlock, 0, s>>>(
-                link_args(i));
-            JG_LAUNCH_CHECK();
-        }
-        std::vector<int32_t> found((size_t)P);
-        copy_d2h(found.data(), t.found.get(), P * sizeof(int32_t), s);
-        const Halo& h = sh.halo_both;
-        t.all_found = 1;
-        for (int q = 0; q < P; ++q)
-            if (q != sh.index && h.recv_off[(size_t)q + 1] > h.recv_off[(size_t)q] && !found[(size_t)h.seg_of(q, sh.index)])
-                t.all_found = 0;
-        cc_link_rest_sharded_kernel<<<red_grid(t.ne), kRedThreads, 0, s>>>(link_args(i), t.linked.get());
-        JG_LAUNCH_CHECK();
-        cc_slots_compress_kernel<<<grid_for(t.sm.total), kBlock, 0, s>>>(t.sm, sh.cc_msg[1].get());
-        JG_LAUNCH_CHECK();
-    }
-    // the label rounds
-    std::vector<void*> mv, rv;
-    for (size_t i = 0; i < ns; ++i) {
-        mv.push_back(g.shards[i]->cc_msg[0].peer());
-        rv.push_back(st[i].rbuf.peer());
-    }
-    for (size_t i = 0; i < ns; ++i) {  // the sparse rounds' marks and counters
-        Shard& sh = *g.shards[i];
-        DeviceGuard dg(sh);
-        St& t = st[i];
-        for (int k = 0; k < 2; ++k) {
-            t.dirty[k].alloc((size_t)std::max<int64_t>((sh.rows + 63) / 64, 1));
-            JG_HIP(hipMemsetAsync(t.dirty[k].get(), 0, t.dirty[k].bytes(), sh.stream));
-        }
-        t.rootb.alloc((size_t)std::max<int64_t>((t.len + 63) / 64, 1));
-        t.cb.alloc((size_t)std::max<int64_t>((t.len + 63) / 64, 1));
-        JG_HIP(hipMemsetAsync(t.rootb.get(), 0, t.rootb.bytes(), sh.stream));
-        JG_HIP(hipMemsetAsync(t.cb.get(), 0, t.cb.bytes(), sh.stream));
-        t.pcnt.alloc(2 * (size_t)P);
-        t.nchg.alloc((size_t)kFellLines * kFellStride);
-        t.cursor.alloc((size_t)P);
-        t.pbase.alloc((size_t)P);
-        t.roffd.alloc((size_t)P + 1);
-    }
-    // One sparse exchange step (the pair counts are in pcnt + cofs per shard): the P x P count matrix
-    // and the dense volume are summed over ranks, so every rank takes the same decision; false = dense
-    // is cheaper (nothing sent).  pack(i) packs shard i's pairs, recv(i) consumes what it received.
-    int64_t dense_fwd = 0;  // elements of one dense exchange over all shards
-    for (size_t i = 0; i < ns; ++i) dense_fwd += st[i].nsend;
-    auto sparse_step = [&](int cofs, auto&& pack, auto&& recv) -> bool {
-        std::vector<std::vector<int64_t>> cnt(ns, std::vector<int64_t>((size_t)P, 0));
-        std::vector<int64_t> mat((size_t)P * P + 1, 0);
-        for (size_t i = 0; i < ns; ++i) {
-            Shard& sh = *g.shards[i];
-            DeviceGuard dg(sh);
-            std::vector<unsigned long long> c((size_t)P);
-            copy_d2h(c.data(), st[i].pcnt.get() + cofs, (size_t)P * sizeof(unsigned long long), sh.stream);
-            for (int q = 0; q < P; ++q) mat[(size_t)sh.index * P + q] = cnt[i][(size_t)q] = (int64_t)c[(size_t)q];
-        }
-        mat[(size_t)P * P] = dense_fwd;
-        allreduce_sum_i64(g, mat.data(), P * P + 1);
-        int64_t pairs_all = 0;
-        for (int64_t k = 0; k < (int64_t)P * P; ++k) pairs_all += mat[(size_t)k];
-        if (2 * pairs_all >= mat[(size_t)P * P]) return false;
-        std::vector<const char*> sp(ns);
-        std::vector<char*> rp(ns);
-        std::vector<std::vector<int64_t>> so(ns), sc(ns), ro(ns), rc(ns);
-        for (size_t i = 0; i < ns; ++i) {
-            Shard& sh = *g.shards[i];
-            DeviceGuard dg(sh);
-            St& t = st[i];
-            so[i].assign((size_t)P + 1, 0);
-            ro[i].assign((size_t)P + 1, 0);
-            sc[i].assign((size_t)P, 0);
-            rc[i].assign((size_t)P, 0);
-            for (int q = 0; q < P; ++q) {
-                sc[i][(size_t)q] = cnt[i][(size_t)q];
-                rc[i][(size_t)q] = mat[(size_t)q * P + sh.index];
-                so[i][(size_t)q + 1] = so[i][(size_t)q] + sc[i][(size_t)q];
-                ro[i][(size_t)q + 1] = ro[i][(size_t)q] + rc[i][(size_t)q];
+            t.sm.total = t.ne + t.sm.cum[t.sm.nseg];
+            int32_t* parent = t.parent();
+            t.tmin.alloc(t.len);
+            t.label.alloc(std::max<int64_t>(sh.rows, 1));
+            t.rank.alloc(std::max<int64_t>(sh.rows, 1));
+            t.found.alloc(P);
+            t.rbuf.alloc(std::max<int64_t>(t.nsend, 1));
+            t.flag.alloc((t.len + 63) / 64);
+            const std::vector<int64_t> woff = halo_word_offsets(h, P);
+            t.sw.alloc(std::max<int64_t>(woff[(size_t)P], 1));
+            t.send_off.alloc(P + 1);
+            t.woff.alloc(P + 1);
+            copy_h2d(t.send_off.get(), h.send_off.data(), (P + 1) * sizeof(int64_t), s);
+            copy_h2d(t.woff.get(), woff.data(), (P + 1) * sizeof(int64_t), s);
+            JG_HIP(hipMemsetAsync(t.found.get(), 0, P * sizeof(int32_t), s));
+            JG_HIP(hipMemsetAsync(t.flag.get(), 0, t.flag.bytes(), s));
+            t.linked.alloc(1);
+            JG_HIP(hipMemsetAsync(t.linked.get(), 0, sizeof(unsigned long long), s));
+            if (sh.rows) {  // labels start at the ranks (cc_prepare_ranks)
+                JG_HIP(hipMemcpyAsync(t.label.get(), sh.cc_rank0.get(), sh.rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+                JG_HIP(hipMemcpyAsync(t.rank.get(), sh.cc_rank0.get(), sh.rows * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
             }
-            if ((int64_t)t.spairs.size() < std::max<int64_t>(so[i][(size_t)P], 1)) t.spairs.alloc(std::max<int64_t>(so[i][(size_t)P], 1));
-            if ((int64_t)t.rpairs.size() < std::max<int64_t>(ro[i][(size_t)P], 1)) t.rpairs.alloc(std::max<int64_t>(ro[i][(size_t)P], 1));
-            copy_h2d(t.pbase.get(), so[i].data(), (size_t)P * sizeof(int64_t), sh.stream);
-            copy_h2d(t.roffd.get(), ro[i].data(), ((size_t)P + 1) * sizeof(int64_t), sh.stream);
-            JG_HIP(hipMemsetAsync(t.cursor.get(), 0, (size_t)P * sizeof(unsigned long long), sh.stream));
-            if (so[i][(size_t)P] > 0) pack(i);
-            sp[i] = reinterpret_cast<const char*>(t.spairs.peer());
-            rp[i] = reinterpret_cast<char*>(t.rpairs.peer());
+            if (t.sm.total) {
+                cc_slots_init_kernel<<<grid_for(t.sm.total), kBlock, 0, s>>>(t.sm, parent);
+                JG_LAUNCH_CHECK();
+            }
+            if (t.ne > 0) {
+                DevBuf<int32_t> sample(1025);
+                uf_link_first_kernel<<<grid_for(t.ne), kBlock, 0, s>>>(parent, c.row_ptr.get(), c.col.get(),
+                                                                       c.first_col.get(), t.ne, kFirst);
+                JG_LAUNCH_CHECK();
+                cc_slots_compress_kernel<<<grid_for(t.sm.total), kBlock, 0, s>>>(t.sm, parent);
+                JG_LAUNCH_CHECK();
+                // the most frequent root among 1024 sampled own rows: the giant tree's
+                uf_sample_kernel<<<4, kBlock, 0, s>>>(parent, t.ne, 1024, sample.get());
+                JG_LAUNCH_CHECK();
+                heavy_rows_kernel<<<1, 1, 0, s>>>(c.row_ptr.get(), t.ne, sample.get() + 1024);
+                JG_LAUNCH_CHECK();
+                std::vector<int32_t> hs(1025);
+                copy_d2h(hs.data(), sample.get(), hs.size() * sizeof(int32_t), s);
+                t.heavy = hs[1024];
+                hs.pop_back();
+                t.giant = most_frequent(hs, &t.giant_share);
+                cc_own_flags_kernel<<<grid_for(((sh.rows + 63) / 64) * kWave), kBlock, 0, s>>>(parent, t.ne, sh.rows, t.giant,
+                                                                                              t.flag.get());
+                JG_LAUNCH_CHECK();
+            }
+            if (woff[(size_t)P] > 0) {
+                cc_pack_flags_kernel<<<grid_for(woff[(size_t)P] * kWave), kBlock, 0, s>>>(
+                    parent, t.giant, h.send_src.get(), t.send_off.get(), t.woff.get(), P, t.sw.get());
+                JG_LAUNCH_CHECK();
+            }
+        });
+    }
+
+    // the copies' flags (in their owner's giant tree), the bounded search, then the second round
+    void second_round() {
+        std::vector<uint64_t*> swv, flv;
+        each([&](CcUfShard& t, Shard&) {
+            swv.push_back(reinterpret_cast<uint64_t*>(t.sw.get()));
+            flv.push_back(reinterpret_cast<uint64_t*>(t.flag.get()));
+        });
+        exchange_halo_bits(g, JG_ADJ_BOTH, swv, flv, false);
+        each([&](CcUfShard& t, Shard& sh) {
+            hipStream_t s = sh.stream;
+            if (t.ne == 0) return;
+            if (tune().cc_uf_search) {  // 0: every peer takes the fallback (a parity-test variant)
+                cc_giant_search_kernel<<<(kCcSearchRows * kCcSearchSplit * kWave + kBlock - 1) / kBlock, kBlock, 0, s>>>(
+                    link_args(t));
+                JG_LAUNCH_CHECK();
+            }
+            std::vector<int32_t> found((size_t)P);
+            copy_d2h(found.data(), t.found.get(), P * sizeof(int32_t), s);
+            const Halo& h = sh.halo_both;
+            t.all_found = 1;
+            for (int q = 0; q < P; ++q)
+                if (q != sh.index && h.recv_off[(size_t)q + 1] > h.recv_off[(size_t)q] && !found[(size_t)h.seg_of(q, sh.index)])
+                    t.all_found = 0;
+            cc_link_rest_sharded_kernel<<<red_grid(t.ne), kRedThreads, 0, s>>>(link_args(t), t.linked.get());
+            JG_LAUNCH_CHECK();
+            cc_slots_compress_kernel<<<grid_for(t.sm.total), kBlock, 0, s>>>(t.sm, t.parent());
+            JG_LAUNCH_CHECK();
+        });
+    }
+
+    // Tree labels over the halo until no own row's label falls: forward (own labels to their copies), apply
+    // (every tree takes its minimum), reverse (the copies' values back to their owners).
+    void label_rounds() {
+        for (CcUfShard& t : sv) {
+            mv.push_back(t.sh->cc_msg[0].peer());
+            rv.push_back(t.rbuf.peer());
+            dense_fwd += t.nsend;
+            own_all += t.ne;
         }
-        exchange_runs(g, sp, so, sc, rp, ro, rc, sizeof(unsigned long long), ncclUint64);
-        for (size_t i = 0; i < ns; ++i) {
-            Shard& sh = *g.shards[i];
-            DeviceGuard dg(sh);
-            if (ro[i][(size_t)P] > 0) recv(i, ro[i][(size_t)P]);
-        }
-        return true;
-    };
-    static const bool debug_rounds = std::getenv("JG_DEBUG_CC") != nullptr;
-    int64_t own_all = 0;  // own rows with an edge, all shards and ranks
-    for (size_t i = 0; i < ns; ++i) own_all += st[i].ne;
-    allreduce_sum_i64(g, &own_all, 1);
-    int64_t dense_all = dense_fwd;
-    allreduce_sum_i64(g, &dense_all, 1);
-    int64_t fell = 0;         // own rows whose label fell last round, all shards and ranks
-    int rounds = 0, cur = 0;  // dirty[cur]: own rows whose label fell last round
-    for (bool any = true; any;) {
-        ++rounds;
-        const int nxt = cur ^ 1;
-        bool fwd_sparse = false;
+        each([&](CcUfShard& t, Shard& sh) {  // the sparse rounds' marks and counters
+            for (int k = 0; k < 2; ++k) {
+                t.dirty[k].alloc((size_t)std::max<int64_t>((sh.rows + 63) / 64, 1));
+                JG_HIP(hipMemsetAsync(t.dirty[k].get(), 0, t.dirty[k].bytes(), sh.stream));
+            }
+            t.rootb.alloc((size_t)std::max<int64_t>((t.len + 63) / 64, 1));
+            t.cb.alloc((size_t)std::max<int64_t>((t.len + 63) / 64, 1));
+            JG_HIP(hipMemsetAsync(t.rootb.get(), 0, t.rootb.bytes(), sh.stream));
+            JG_HIP(hipMemsetAsync(t.cb.get(), 0, t.cb.bytes(), sh.stream));
+            t.pcnt.alloc(2 * (size_t)P);
+            t.nchg.alloc((size_t)kFellLines * kFellStride);
+            t.cursor.alloc((size_t)P);
+            t.pbase.alloc((size_t)P);
+            t.roffd.alloc((size_t)P + 1);
+        });
+        allreduce_sum_i64(g, &own_all, 1);
+        dense_all = dense_fwd;
+        allreduce_sum_i64(g, &dense_all, 1);
+        do {
+            ++rounds;
+            forward();
+            apply();
+            reverse();
+            if (fwd_sparse)
+                each([&](CcUfShard& t, Shard& sh) {  // the marks of this round's sparse apply
+                    JG_HIP(hipMemsetAsync(t.rootb.get(), 0, t.rootb.bytes(), sh.stream));
+                    JG_HIP(hipMemsetAsync(t.cb.get(), 0, t.cb.bytes(), sh.stream));
+                });
+            if (cc_debug())
+                each([&](CcUfShard& t, Shard& sh) {
+                    std::vector<unsigned long long> c(2 * (size_t)P, 0);
+                    copy_d2h(c.data(), t.pcnt.get(), c.size() * sizeof(unsigned long long), sh.stream);
+                    unsigned long long f = 0, rv2 = 0;
+                    for (int q = 0; q < P; ++q) f += c[(size_t)q], rv2 += c[(size_t)P + q];
+                    std::fprintf(stderr, "[jg cc] round %d shard %d: forward %s %llu pairs, reverse %s %llu pairs (rows fell "
+                                 "last round, all shards: %lld)\n", rounds, sh.index, fwd_sparse ? "sparse" : "dense", f,
+                                 rev_sparse ? "sparse" : "dense", rv2, (long long)fell);
+                });
+            fell = 0;  // (cc_changed is set exactly when a shard's count is non-zero)
+            each([&](CcUfShard& t, Shard& sh) {
+                std::vector<unsigned long long> c((size_t)kFellLines * kFellStride);
+                copy_d2h(c.data(), t.nchg.get(), c.size() * sizeof(unsigned long long), sh.stream);
+                for (int k = 0; k < kFellLines; ++k) fell += (int64_t)c[(size_t)k * kFellStride];
+            });
+            allreduce_sum_i64(g, &fell, 1);
+            cur ^= 1;
+        } while (fell > 0);
+    }
+
+    // One sparse exchange step of the pair counts at pcnt + cofs (exchange_pairs_sparse; false = dense is
+    // cheaper, nothing sent).  pack(t, sh) packs a shard's pairs, recv(t, sh, n) consumes the n it received.
+    template <class Pack, class Recv>
+    bool sparse_step(int cofs, Pack&& pack, Recv&& recv) {
+        std::vector<const unsigned long long*> counts;
+        each([&](CcUfShard& t, Shard&) { counts.push_back(t.pcnt.get() + cofs); });
+        return exchange_pairs_sparse(
+            g, counts, dense_fwd, 1,
+            [&](size_t i, const std::vector<int64_t>& so, const std::vector<int64_t>& ro) {
+                CcUfShard& t = sv[i];
+                hipStream_t s = t.sh->stream;
+                const int64_t nso = std::max<int64_t>(so[(size_t)P], 1), nro = std::max<int64_t>(ro[(size_t)P], 1);
+                if ((int64_t)t.spairs.size() < nso) t.spairs.alloc(nso);
+                if ((int64_t)t.rpairs.size() < nro) t.rpairs.alloc(nro);
+                copy_h2d(t.pbase.get(), so.data(), (size_t)P * sizeof(int64_t), s);
+                copy_h2d(t.roffd.get(), ro.data(), ((size_t)P + 1) * sizeof(int64_t), s);
+                JG_HIP(hipMemsetAsync(t.cursor.get(), 0, (size_t)P * sizeof(unsigned long long), s));
+                if (so[(size_t)P] > 0) pack(t, *t.sh);
+                return std::make_pair(reinterpret_cast<const char*>(t.spairs.peer()),
+                                      reinterpret_cast<char*>(t.rpairs.peer()));
+            },
+            [&](size_t i, int64_t n) { recv(sv[i], *sv[i].sh, n); });
+    }
+
+    void forward() {
+        fwd_sparse = false;
         // a sparse forward is tried when the rows that fell, at the mean send-list fan-out, would make
         // fewer pairs than half the dense run (the counts then decide; rounds 2-3 of RMAT move most labels)
-        const bool try_sparse = rounds > 1 && tune().cc_sparse && P <= kMaxPeersCc &&
-                                2.0 * (double)fell * (double)dense_all / (double)std::max<int64_t>(own_all, 1) <
-                                    (double)dense_all;
-        if (try_sparse) {
-            for (size_t i = 0; i < ns; ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                St& t = st[i];
+        if (rounds > 1 && tune().cc_sparse && P <= kMaxPeersCc &&
+            2.0 * (double)fell * (double)dense_all / (double)std::max<int64_t>(own_all, 1) < (double)dense_all) {
+            each([&](CcUfShard& t, Shard& sh) {
                 JG_HIP(hipMemsetAsync(t.pcnt.get(), 0, 2 * (size_t)P * sizeof(unsigned long long), sh.stream));
                 if (t.nsend) {
                     cc_fwd_count_kernel<<<grid_for(t.nsend), kBlock, 0, sh.stream>>>(
@@ -1384,85 +1399,80 @@ bool cc_union_find_sharded(Graph& g, int* iterations, int* rounds_out, double* w
                     JG_LAUNCH_CHECK();
                 }
                 bytes += 4.0 * (double)t.nsend;  // send_src (the dirty bits are 1/32 of it)
-            }
+            });
             fwd_sparse = sparse_step(
                 0,
-                [&](size_t i) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
+                [&](CcUfShard& t, Shard& sh) {
                     cc_fwd_pack_kernel<<<grid_for(t.nsend), kBlock, 0, sh.stream>>>(
                         sh.halo_both.send_src.get(), t.send_off.get(), P, t.dirty[cur].get(), t.label.get(), t.pbase.get(),
                         t.cursor.get(), t.spairs.get());
                     JG_LAUNCH_CHECK();
                 },
-                [&](size_t i, int64_t n) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
+                [&](CcUfShard& t, Shard& sh, int64_t n) {
                     cc_fwd_recv_kernel<<<grid_for(n), kBlock, 0, sh.stream>>>(t.rpairs.get(), t.roffd.get(), P, sh.index,
-                                                                             sh.halo_both.tbits, sh.cc_msg[1].get(),
+                                                                             sh.halo_both.tbits, t.parent(),
                                                                              sh.cc_msg[0].get(), t.tmin.get(), t.rootb.get());
                     JG_LAUNCH_CHECK();
                     bytes += 24.0 * (double)n;  // pair, parent, msg, tmin
                 });
         }
         if (!fwd_sparse) {
-            for (size_t i = 0; i < ns; ++i) {  // own labels into the message vector's own part
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                if (st[i].ne)
-                    JG_HIP(hipMemcpyAsync(sh.cc_msg[0].get(), st[i].label.get(), st[i].ne * sizeof(int32_t),
-                                          hipMemcpyDeviceToDevice, sh.stream));
-            }
+            each([&](CcUfShard& t, Shard& sh) {  // own labels into the message vector's own part
+                if (t.ne)
+                    JG_HIP(hipMemcpyAsync(sh.cc_msg[0].get(), t.label.get(), t.ne * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                          sh.stream));
+            });
             exchange_msg(g, 0);
         }
-        for (size_t i = 0; i < ns; ++i) {
-            Shard& sh = *g.shards[i];
-            DeviceGuard dg(sh);
-            St& t = st[i];
+    }
+
+    void apply() {
+        const int nxt = cur ^ 1;
+        each([&](CcUfShard& t, Shard& sh) {
             JG_HIP(hipMemsetAsync(sh.cc_changed.get(), 0, sizeof(int32_t), sh.stream));
             JG_HIP(hipMemsetAsync(t.dirty[nxt].get(), 0, t.dirty[nxt].bytes(), sh.stream));
             JG_HIP(hipMemsetAsync(t.nchg.get(), 0, t.nchg.bytes(), sh.stream));
             if (!fwd_sparse) JG_HIP(hipMemsetAsync(t.pcnt.get(), 0, 2 * (size_t)P * sizeof(unsigned long long), sh.stream));
-            if (t.ne == 0) continue;
+            if (t.ne == 0) return;
             const unsigned grid = grid_for(t.sm.total);
             if (fwd_sparse) {
                 cc_own_tree_min_kernel<<<grid_for(t.ne), kBlock, 0, sh.stream>>>(t.dirty[cur].get(), t.ne, t.label.get(),
-                                                                                 sh.cc_msg[1].get(), t.tmin.get(),
-                                                                                 t.rootb.get());
+                                                                                 t.parent(), t.tmin.get(), t.rootb.get());
                 JG_LAUNCH_CHECK();
                 cc_apply_sparse_kernel<<<grid, kBlock, 0, sh.stream>>>(
-                    t.sm, sh.cc_msg[1].get(), t.tmin.get(), t.rootb.get(), t.label.get(), sh.cc_msg[0].get(),
-                    t.dirty[nxt].get(), t.cb.get(), sh.index, P, sh.halo_both.tbits, t.pcnt.get() + P, sh.cc_changed.get(),
-                    t.nchg.get());
+                    t.sm, t.parent(), t.tmin.get(), t.rootb.get(), t.label.get(), sh.cc_msg[0].get(), t.dirty[nxt].get(),
+                    t.cb.get(), sh.index, P, sh.halo_both.tbits, t.pcnt.get() + P, sh.cc_changed.get(), t.nchg.get());
                 JG_LAUNCH_CHECK();
                 // dirty bits of own rows, parent + root bit per slot (the applied slots' tmin and values are few)
                 bytes += (double)t.ne / 8.0 + 4.5 * (double)t.sm.total;
-                continue;
+                return;
             }
             if (rounds == 1) {
                 cc_tree_init_kernel<<<grid, kBlock, 0, sh.stream>>>(t.sm, t.label.get(), sh.cc_msg[0].get(), t.tmin.get());
                 JG_LAUNCH_CHECK();
             }
             cc_tree_min_kernel<<<red_grid(t.sm.total), kRedThreads, 0, sh.stream>>>(
-                t.sm, sh.cc_msg[1].get(), t.label.get(), sh.cc_msg[0].get(), t.giant, t.tmin.get());
+                t.sm, t.parent(), t.label.get(), sh.cc_msg[0].get(), t.giant, t.tmin.get());
             JG_LAUNCH_CHECK();
-            cc_tree_apply_kernel<<<grid, kBlock, 0, sh.stream>>>(t.sm, sh.cc_msg[1].get(), t.tmin.get(), t.label.get(),
+            cc_tree_apply_kernel<<<grid, kBlock, 0, sh.stream>>>(t.sm, t.parent(), t.tmin.get(), t.label.get(),
                                                                  sh.cc_msg[0].get(), sh.cc_changed.get(), t.dirty[nxt].get(),
                                                                  t.nchg.get());
             JG_LAUNCH_CHECK();
             // per slot: init 8 B (round 1), tree minima 8 B (parent, label; the atomics of non-root
             // members), apply 12 B
             bytes += (rounds == 1 ? 28.0 : 20.0) * (double)t.sm.total;
-        }
-        // reverse: after a sparse apply only the marked copies moved (pairs, unless dense is cheaper);
-        // after a dense one every copy holds its tree's minimum (the whole run)
-        bool rev_sparse = false;
+        });
+    }
+
+    // reverse: after a sparse apply only the marked copies moved (pairs, unless dense is cheaper);
+    // after a dense one every copy holds its tree's minimum (the whole run)
+    void reverse() {
+        const int nxt = cur ^ 1;
+        rev_sparse = false;
         if (fwd_sparse)
             rev_sparse = sparse_step(
                 P,
-                [&](size_t i) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
+                [&](CcUfShard& t, Shard& sh) {
                     if (t.sm.total > t.ne) {
                         cc_rev_pack_kernel<<<grid_for(t.sm.total - t.ne), kBlock, 0, sh.stream>>>(
                             t.sm, t.cb.get(), sh.cc_msg[0].get(), sh.index, P, sh.halo_both.tbits, t.pbase.get(),
@@ -1470,99 +1480,69 @@ bool cc_union_find_sharded(Graph& g, int* iterations, int* rounds_out, double* w
                         JG_LAUNCH_CHECK();
                     }
                 },
-                [&](size_t i, int64_t n) {
-                    Shard& sh = *g.shards[i];
-                    St& t = st[i];
-                    cc_rev_recv_kernel<<<grid_for(n), kBlock, 0, sh.stream>>>(t.rpairs.get(), t.roffd.get(), P,
-                                                                             sh.halo_both.send_src.get(), t.send_off.get(),
-                                                                             t.label.get(), t.dirty[nxt].get(),
-                                                                             sh.cc_changed.get(), t.nchg.get());
+                [&](CcUfShard& t, Shard& sh, int64_t n) {
+                    cc_rev_recv_kernel<<<grid_for(n), kBlock, 0, sh.stream>>>(
+                        t.rpairs.get(), t.roffd.get(), P, sh.halo_both.send_src.get(), t.send_off.get(), t.label.get(),
+                        t.dirty[nxt].get(), sh.cc_changed.get(), t.nchg.get());
                     JG_LAUNCH_CHECK();
                     bytes += 20.0 * (double)n;  // pair, send_src, label
                 });
-        if (!rev_sparse) {
-            exchange_halo_reverse(g, JG_ADJ_BOTH, mv, rv, sizeof(int32_t), ncclInt32);
-            for (size_t i = 0; i < ns; ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                St& t = st[i];
-                if (t.nsend) {
-                    cc_reverse_apply_kernel<<<grid_for(t.nsend), kBlock, 0, sh.stream>>>(
-                        t.rbuf.get(), sh.halo_both.send_src.get(), t.nsend, t.label.get(), sh.cc_changed.get(),
-                        t.dirty[nxt].get(), t.nchg.get());
-                    JG_LAUNCH_CHECK();
-                }
-                bytes += 12.0 * (double)t.nsend;  // reverse apply per send-list element
+        if (rev_sparse) return;
+        exchange_halo_reverse(g, JG_ADJ_BOTH, mv, rv, sizeof(int32_t), ncclInt32);
+        each([&](CcUfShard& t, Shard& sh) {
+            if (t.nsend) {
+                cc_reverse_apply_kernel<<<grid_for(t.nsend), kBlock, 0, sh.stream>>>(
+                    t.rbuf.get(), sh.halo_both.send_src.get(), t.nsend, t.label.get(), sh.cc_changed.get(),
+                    t.dirty[nxt].get(), t.nchg.get());
+                JG_LAUNCH_CHECK();
             }
-        }
-        if (fwd_sparse)
-            for (size_t i = 0; i < ns; ++i) {  // the marks of this round's sparse apply
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                JG_HIP(hipMemsetAsync(st[i].rootb.get(), 0, st[i].rootb.bytes(), sh.stream));
-                JG_HIP(hipMemsetAsync(st[i].cb.get(), 0, st[i].cb.bytes(), sh.stream));
-            }
-        if (debug_rounds) {
-            for (size_t i = 0; i < ns; ++i) {
-                Shard& sh = *g.shards[i];
-                DeviceGuard dg(sh);
-                std::vector<unsigned long long> c(2 * (size_t)P, 0);
-                copy_d2h(c.data(), st[i].pcnt.get(), c.size() * sizeof(unsigned long long), sh.stream);
-                unsigned long long f = 0, rv2 = 0;
-                for (int q = 0; q < P; ++q) f += c[(size_t)q], rv2 += c[(size_t)P + q];
-                std::fprintf(stderr, "[jg cc] round %d shard %d: forward %s %llu pairs, reverse %s %llu pairs (rows fell "
-                             "last round, all shards: %lld)\n", rounds, sh.index, fwd_sparse ? "sparse" : "dense", f,
-                             rev_sparse ? "sparse" : "dense", rv2, (long long)fell);
-            }
-        }
-        fell = 0;  // (cc_changed is set exactly when a shard's count is non-zero)
-        for (size_t i = 0; i < ns; ++i) {
-            Shard& sh = *g.shards[i];
-            DeviceGuard dg(sh);
-            std::vector<unsigned long long> c((size_t)kFellLines * kFellStride);
-            copy_d2h(c.data(), st[i].nchg.get(), c.size() * sizeof(unsigned long long), sh.stream);
-            for (int k = 0; k < kFellLines; ++k) fell += (int64_t)c[(size_t)k * kFellStride];
-        }
-        allreduce_sum_i64(g, &fell, 1);
-        any = fell > 0;
-        cur = nxt;
+            bytes += 12.0 * (double)t.nsend;  // reverse apply per send-list element
+        });
     }
-    // the superstep count: one BFS from every component's minimum-rank vertex
-    std::vector<CcRoots> roots(ns);
-    for (size_t i = 0; i < ns; ++i) roots[i] = CcRoots{st[i].label.peer(), st[i].rank.peer(), nullptr, st[i].ne};  // (used under shard i)
-    double reached = 0;
-    const int d = cc_root_eccentricity_sharded(g, roots.data(), &reached);
-    const int it = d + 1;  // 0 when no vertex has an edge (d = -1)
-    *rounds_out = rounds;
-    static const bool debug = std::getenv("JG_DEBUG_CC") != nullptr;
-    unsigned long long lk = 0;
-    for (size_t i = 0; i < ns; ++i) {
-        Shard& sh = *g.shards[i];
-        DeviceGuard dg(sh);
-        St& t = st[i];
-        unsigned long long l = 0;
-        copy_d2h(&l, t.linked.get(), sizeof l, sh.stream);
-        lk += l;
-        if (debug)
-            std::fprintf(stderr, "[jg cc] shard %d: rows %lld with edges %lld, vector %lld, entries %lld, giant root %d "
-                         "(%d of 1024 sampled), all peers found %d, rest entries scanned %llu; %d label rounds, "
-                         "%d supersteps\n",
-                         sh.index, (long long)sh.rows, (long long)t.ne, (long long)t.len, (long long)sh.both.nnz,
-                         t.giant, t.giant_share, t.all_found, l, rounds, it);
-        // per slot: init 4 B, two compressions 16 B; flags 1 bit per vector position; per row with an
-        // edge: first links 20 B, BFS start 17 B, depth and frontier probe 5 B
-        bytes += 20.0 * (double)t.sm.total + (double)t.len / 8.0 + 42.0 * (double)t.ne;
-        if (it <= kCcMaxIterations - 1 && sh.rows)
-            JG_HIP(hipMemcpyAsync(sh.cc_label.get(), t.label.get(), sh.rows * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                                  sh.stream));
-        JG_HIP(hipStreamSynchronize(sh.stream));
+
+    // the superstep count (one BFS from every component's minimum-rank vertex), the byte model, the labels
+    bool finish(int* iterations, double* work_bytes) {
+        std::vector<CcRoots> roots;
+        for (CcUfShard& t : sv) roots.push_back(CcRoots{t.label.peer(), t.rank.peer(), nullptr, t.ne});  // (used under its shard)
+        double reached = 0;
+        const int d = cc_root_eccentricity_sharded(g, roots.data(), &reached);
+        const int it = d + 1;  // 0 when no vertex has an edge (d = -1)
+        unsigned long long lk = 0;
+        each([&](CcUfShard& t, Shard& sh) {
+            unsigned long long l = 0;
+            copy_d2h(&l, t.linked.get(), sizeof l, sh.stream);
+            lk += l;
+            if (cc_debug())
+                std::fprintf(stderr, "[jg cc] shard %d: rows %lld with edges %lld, vector %lld, entries %lld, giant root %d "
+                             "(%d of 1024 sampled), all peers found %d, rest entries scanned %llu; %d label rounds, "
+                             "%d supersteps\n",
+                             sh.index, (long long)sh.rows, (long long)t.ne, (long long)t.len, (long long)sh.both.nnz,
+                             t.giant, t.giant_share, t.all_found, l, rounds, it);
+            // per slot: init 4 B, two compressions 16 B; flags 1 bit per vector position; per row with an
+            // edge: first links 20 B, BFS start 17 B, depth and frontier probe 5 B
+            bytes += 20.0 * (double)t.sm.total + (double)t.len / 8.0 + 42.0 * (double)t.ne;
+            if (it <= kCcMaxIterations - 1 && sh.rows)
+                JG_HIP(hipMemcpyAsync(sh.cc_label.get(), t.label.get(), sh.rows * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                      sh.stream));
+            JG_HIP(hipStreamSynchronize(sh.stream));
+        });
+        if (it > kCcMaxIterations - 1) return false;
+        // 12 B per entry linked (col, both finds), 4 B per adjacency entry of the rows the BFS reached
+        *work_bytes = bytes + 12.0 * (double)lk + 4.0 * reached;
+        *iterations = it;
+        return true;
     }
-    if (it > kCcMaxIterations - 1) return false;
-    // 12 B per entry linked (col, both finds), 4 B per adjacency entry of the rows the BFS reached
-    *work_bytes = bytes + 12.0 * (double)lk + 4.0 * reached;
-    *iterations = it;
-    return true;
-}
+
+    Graph& g;
+    const int P, kFirst;
+    std::vector<CcUfShard> sv;  // per local shard
+    std::vector<void*> mv, rv;  // the dense reverse exchange's message vectors and receive buffers
+    double bytes = 0;           // the byte model's running sum
+    int64_t dense_fwd = 0, dense_all = 0;  // elements of one dense exchange over the local shards / all ranks
+    int64_t own_all = 0, fell = 0;  // own rows with an edge / whose label fell last round, all shards and ranks
+    int rounds = 0, cur = 0;    // dirty[cur]: own rows whose label fell last round
+    bool fwd_sparse = false, rev_sparse = false;  // what this round's exchanges took
+};
 
 }  // namespace
 
@@ -1634,9 +1614,54 @@ void cc_prepare_ranks(Graph& g) {
 }
 
 namespace {
-// Superstep 0 of the propagation: labels = ranks, only vertices with an edge send (every shard), then
-// the exchange step.
-void cc_propagation_init(Graph& g) {
+struct CcPushScratch {  // the push supersteps' scratch (one shard)
+    DevBuf<int32_t> queue, touched;
+    DevBuf<int64_t> qoff, touched_off;
+    DevBuf<unsigned long long> ctr;
+};
+
+CcOp cc_op(Graph& g, Shard& sh, int cur) {  // a superstep reading cc_msg[cur]
+    CcOp op;
+    op.msg = sh.cc_msg[cur].get();
+    op.msg_out = sh.cc_msg[cur ^ 1].get();
+    op.label = sh.cc_label.get();
+    op.changed = sh.cc_changed.get();
+    op.pos = g.vec_pos(sh, JG_ADJ_BOTH);
+    return op;
+}
+
+// One shard: a push-style superstep.  false (only the senders' queue made) when the senders have too many edges.
+bool cc_push_superstep(Graph& g, CcPushScratch& pu, int cur) {
+    Shard& sh = *g.shards[0];
+    JG_HIP(hipMemsetAsync(pu.ctr.get(), 0, 2 * sizeof(unsigned long long), sh.stream));
+    cc_senders_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(sh.cc_msg[cur].get(), sh.rows, sh.both.row_ptr.get(),
+                                                                   pu.queue.get(), pu.qoff.get(), pu.ctr.get());
+    JG_LAUNCH_CHECK();
+    unsigned long long h = 0;
+    copy_d2h(&h, pu.ctr.get(), sizeof h, sh.stream);
+    const int64_t nq = (int64_t)(h >> kPackShift), mf = (int64_t)(h & kEdgeMask);
+    if (!((double)mf < (double)sh.both.nnz / (double)tune().bfs_alpha)) return false;
+    JG_HIP(hipMemsetAsync(sh.cc_changed.get(), 0, sizeof(int32_t), sh.stream));
+    JG_HIP(hipMemsetAsync(sh.cc_msg[cur ^ 1].get(), 0x7F, sh.cc_msg[cur ^ 1].bytes(), sh.stream));
+    if (mf == 0) return true;
+    CcPush a{pu.queue.get(), pu.qoff.get(), nq, mf, sh.both.row_ptr.get(), sh.both.col.get(), sh.cc_msg[cur].get(),
+             sh.cc_msg[cur ^ 1].get(), pu.touched.get(), pu.touched_off.get(), pu.ctr.get() + 1};
+    cc_push_kernel<<<(unsigned)std::min<int64_t>(std::max<int64_t>((mf / 4 + kBlock - 1) / kBlock, 1), 4096), kBlock, 0,
+                     sh.stream>>>(a);
+    JG_LAUNCH_CHECK();
+    copy_d2h(&h, pu.ctr.get() + 1, sizeof h, sh.stream);
+    const int64_t nt = (int64_t)(h >> kPackShift);
+    if (nt > 0) {
+        cc_push_apply_kernel<<<grid_for(nt), kBlock, 0, sh.stream>>>(pu.touched.get(), nt, cc_op(g, sh, cur));
+        JG_LAUNCH_CHECK();
+    }
+    return true;
+}
+
+// The label propagation: superstep 0 (labels = ranks, only vertices with an edge send, then the exchange
+// step), then pull supersteps (pu: on one shard, push-style ones while the senders have few edges) until no
+// label changes.  any: superstep 0's vote (anyone with an edge sent, all ranks).  Returns the superstep count.
+int cc_propagate(Graph& g, CcPushScratch* pu, int any) {
     for (auto& sp : g.shards) {
         Shard& sh = *sp;
         DeviceGuard dg(sh);
@@ -1649,6 +1674,49 @@ void cc_propagation_init(Graph& g) {
         }
     }
     exchange_msg(g, 0);
+    int iteration = 0, cur = 0;
+    while (any && iteration < kCcMaxIterations - 1) {
+        ++iteration;
+        if (!(pu && cc_push_superstep(g, *pu, cur)))
+            for (auto& sp : g.shards) {
+                Shard& sh = *sp;
+                DeviceGuard dg(sh);
+                JG_HIP(hipMemsetAsync(sh.cc_changed.get(), 0, sizeof(int32_t), sh.stream));
+                launch_pull(sh.both, sh.plan_both, cc_op(g, sh, cur), sh.cc_hub_partial.get(), sh.stream,
+                            g.ctx->profiling ? g.ctx : nullptr, &sh, sh.cc_split_partial.get());
+            }
+        exchange_msg(g, cur ^ 1);
+        any = 0;
+        for (auto& sp : g.shards) {
+            Shard& sh = *sp;
+            DeviceGuard dg(sh);
+            int32_t ch = 0;
+            JG_HIP(hipMemcpyAsync(&ch, sh.cc_changed.get(), sizeof ch, hipMemcpyDeviceToHost, sh.stream));
+            JG_HIP(hipStreamSynchronize(sh.stream));
+            any |= ch;
+        }
+        any = allreduce_or(g, any);
+        cur ^= 1;
+    }
+    return iteration;
+}
+
+// Sharded graphs: the caller-order ids from every shard's labels, on the host.  solved: a union-find's
+// labels of shard 0 are uf_labels, of its first uf_label_rows rows.
+void cc_assemble_on_host(Graph& g, bool solved, const int32_t* uf_labels, int64_t uf_label_rows, int64_t* comp_out) {
+    const std::vector<int64_t>& vid_of_rank = g.vid_of_rank();
+    for (auto& sp : g.shards) {
+        Shard& sh = *sp;
+        DeviceGuard dg(sh);
+        std::vector<int32_t> h(sh.rows);
+        const bool uf = solved && &sh == &*g.shards[0];
+        const int32_t* lab = uf ? uf_labels : sh.cc_label.get();
+        const int64_t lr = uf ? std::min(uf_label_rows, sh.rows) : sh.rows;
+        if (lr) copy_d2h(h.data(), lab, lr * sizeof(int32_t), sh.stream);
+        if (lr < sh.rows)  // the union-find's edgeless suffix: its ranks
+            copy_d2h(h.data() + lr, sh.cc_rank0.get() + lr, (sh.rows - lr) * sizeof(int32_t), sh.stream);
+        for (int64_t l = 0; l < sh.rows; ++l) comp_out[sh.dense_of_local()[l]] = vid_of_rank[h[l]];
+    }
 }
 }  // namespace
 
@@ -1696,14 +1764,9 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelH
     prof_discard_exchanges(g);  // exchange pairs count from t0 on only
     region_mark(sh0.stream, true);
     JG_HIP(hipEventRecord(t0, sh0.stream));
-    int iteration = 0, cur = 0;
     // one shard: supersteps whose senders have few edges run push-style
     const bool push_ok = g.shards.size() == 1 && g.P == 1 && tune().cc_push;
-    struct Push {
-        DevBuf<int32_t> queue, touched;
-        DevBuf<int64_t> qoff, touched_off;
-        DevBuf<unsigned long long> ctr;
-    } pu;
+    CcPushScratch pu;
     if (push_ok) {
         const size_t r1 = (size_t)std::max<int64_t>(sh0.rows, 1);
         pu.queue.alloc(r1);
@@ -1713,6 +1776,7 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelH
         pu.ctr.alloc(2);
     }
     // One shard: the same labels and superstep count from a union-find and one BFS (cc_union_find).
+    int iteration = 0;
     bool solved = false;
     const int32_t* uf_labels = nullptr;  // the union-find's labels of shard 0 (when solved)
     int64_t uf_label_rows = sh0.rows;      // its rows from here on take their rank (cc_union_find)
@@ -1745,84 +1809,13 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelH
         solved = cc_union_find(ctx, sh0, &iteration, &uf_labels, &uf_label_rows, &uf_bytes, dev_out ? &emit_output : nullptr,
                                dev_out ? t1 : nullptr);
     // Sharded over halo plans: the same from local union-finds, tree labels over the halo and a sharded BFS
-    // (cc_union_find_sharded); the sharded BFS takes at most 64 shards (jg_traverse.hip, kMaxShardsBfs).
-    int uf_rounds = 0;
+    // (CcShardedUf); the sharded BFS takes at most 64 shards (jg_traverse.hip, kMaxShardsBfs).
     if (!solved && !uf_one && g.P > 1 && g.P <= 64 && sh0.halo_both.on && tune().cc_uf && tune().cc_uf_sharded) {
-        solved = cc_union_find_sharded(g, &iteration, &uf_rounds, &uf_bytes);
+        solved = CcShardedUf(g).run(&iteration, &uf_bytes);
         if (solved) uf_labels = sh0.cc_label.get();
     }
     // the propagation (no union-find path, or the 99-superstep cap binds): from superstep 0
-    if (!solved) {
-        iteration = 0;
-        cc_propagation_init(g);
-    }
-    while (!solved && any && iteration < kCcMaxIterations - 1) {
-        ++iteration;
-        bool pushed = false;
-        if (push_ok) {
-            Shard& sh = sh0;
-            JG_HIP(hipMemsetAsync(pu.ctr.get(), 0, 2 * sizeof(unsigned long long), sh.stream));
-            cc_senders_kernel<<<grid_for(sh.rows), kBlock, 0, sh.stream>>>(sh.cc_msg[cur].get(), sh.rows,
-                                                                           sh.both.row_ptr.get(), pu.queue.get(),
-                                                                           pu.qoff.get(), pu.ctr.get());
-            JG_LAUNCH_CHECK();
-            unsigned long long h = 0;
-            copy_d2h(&h, pu.ctr.get(), sizeof h, sh.stream);
-            const int64_t nq = (int64_t)(h >> kPackShift), mf = (int64_t)(h & kEdgeMask);
-            if ((double)mf < (double)sh.both.nnz / (double)tune().bfs_alpha) {
-                pushed = true;
-                JG_HIP(hipMemsetAsync(sh.cc_changed.get(), 0, sizeof(int32_t), sh.stream));
-                JG_HIP(hipMemsetAsync(sh.cc_msg[cur ^ 1].get(), 0x7F, sh.cc_msg[cur ^ 1].bytes(), sh.stream));
-                if (mf > 0) {
-                    CcPush a{pu.queue.get(), pu.qoff.get(), nq, mf, sh.both.row_ptr.get(), sh.both.col.get(),
-                             sh.cc_msg[cur].get(), sh.cc_msg[cur ^ 1].get(), pu.touched.get(), pu.touched_off.get(),
-                             pu.ctr.get() + 1};
-                    cc_push_kernel<<<(unsigned)std::min<int64_t>(std::max<int64_t>((mf / 4 + kBlock - 1) / kBlock, 1),
-                                                                  4096),
-                                     kBlock, 0, sh.stream>>>(a);
-                    JG_LAUNCH_CHECK();
-                    copy_d2h(&h, pu.ctr.get() + 1, sizeof h, sh.stream);
-                    const int64_t nt = (int64_t)(h >> kPackShift);
-                    if (nt > 0) {
-                        CcOp op;
-                        op.msg = sh.cc_msg[cur].get();
-                        op.msg_out = sh.cc_msg[cur ^ 1].get();
-                        op.label = sh.cc_label.get();
-                        op.changed = sh.cc_changed.get();
-                        op.pos = g.vec_pos(sh, JG_ADJ_BOTH);
-                        cc_push_apply_kernel<<<grid_for(nt), kBlock, 0, sh.stream>>>(pu.touched.get(), nt, op);
-                        JG_LAUNCH_CHECK();
-                    }
-                }
-            }
-        }
-        if (!pushed)
-        for (auto& sp : g.shards) {
-            Shard& sh = *sp;
-            DeviceGuard dg(sh);
-            JG_HIP(hipMemsetAsync(sh.cc_changed.get(), 0, sizeof(int32_t), sh.stream));
-            CcOp op;
-            op.msg = sh.cc_msg[cur].get();
-            op.msg_out = sh.cc_msg[cur ^ 1].get();
-            op.label = sh.cc_label.get();
-            op.changed = sh.cc_changed.get();
-            op.pos = g.vec_pos(sh, JG_ADJ_BOTH);
-            launch_pull(sh.both, sh.plan_both, op, sh.cc_hub_partial.get(), sh.stream, ctx.profiling ? &ctx : nullptr,
-                        &sh, sh.cc_split_partial.get());
-        }
-        exchange_msg(g, cur ^ 1);
-        any = 0;
-        for (auto& sp : g.shards) {
-            Shard& sh = *sp;
-            DeviceGuard dg(sh);
-            int32_t ch = 0;
-            JG_HIP(hipMemcpyAsync(&ch, sh.cc_changed.get(), sizeof ch, hipMemcpyDeviceToHost, sh.stream));
-            JG_HIP(hipStreamSynchronize(sh.stream));
-            any |= ch;
-        }
-        any = allreduce_or(g, any);
-        cur ^= 1;
-    }
+    if (!solved) iteration = cc_propagate(g, push_ok ? &pu : nullptr, any);
     // the union-find queued the output behind its BFS start; the other paths (and a union-find that hit
     // the superstep cap, whose output is stale) make it here
     // (an edgeless graph's union-find returns before its BFS and queues nothing: out_done is still false)
@@ -1863,19 +1856,7 @@ void cc_run(Graph& g, int64_t* comp_out, int32_t* iterations_out, const CcLabelH
         DeviceGuard dg(sh);
         copy_d2h(comp_out, out.get(), n * sizeof(int64_t), sh.stream);
     } else if (comp_out) {
-        const std::vector<int64_t>& vid_of_rank = g.vid_of_rank();
-        for (auto& sp : g.shards) {
-            Shard& sh = *sp;
-            DeviceGuard dg(sh);
-            std::vector<int32_t> h(sh.rows);
-            const bool uf = solved && &sh == &sh0;
-            const int32_t* lab = uf ? uf_labels : sh.cc_label.get();
-            const int64_t lr = uf ? std::min(uf_label_rows, sh.rows) : sh.rows;
-            if (lr) copy_d2h(h.data(), lab, lr * sizeof(int32_t), sh.stream);
-            if (lr < sh.rows)  // the union-find's edgeless suffix: its ranks
-                copy_d2h(h.data() + lr, sh.cc_rank0.get() + lr, (sh.rows - lr) * sizeof(int32_t), sh.stream);
-            for (int64_t l = 0; l < sh.rows; ++l) comp_out[sh.dense_of_local()[l]] = vid_of_rank[h[l]];
-        }
+        cc_assemble_on_host(g, solved, uf_labels, uf_label_rows, comp_out);
     }
     prof_collect(ctx, g);
 }

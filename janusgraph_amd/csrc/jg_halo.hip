@@ -564,7 +564,10 @@ void exchange_halo_bits_both(Graph& g, uint32_t adj, std::vector<uint64_t*>& fse
     rccl_check(ncclGroupEnd(), "ncclGroupEnd");
 }
 
-void exchange_runs(Graph& g, const std::vector<const char*>& send, const std::vector<std::vector<int64_t>>& soff,
+// Per-peer runs whose lengths both sides know (exchange_pairs_sparse): local shard i sends scount[i][q]
+// elements from send[i] + soff[i][q] to peer q and receives rcount[i][q] elements from q at
+// recv[i] + roff[i][q] (offsets and counts in elements of eb bytes).
+static void exchange_runs(Graph& g, const std::vector<const char*>& send, const std::vector<std::vector<int64_t>>& soff,
                    const std::vector<std::vector<int64_t>>& scount, const std::vector<char*>& recv,
                    const std::vector<std::vector<int64_t>>& roff, const std::vector<std::vector<int64_t>>& rcount,
                    size_t eb, ncclDataType_t type) {
@@ -633,6 +636,47 @@ void exchange_runs(Graph& g, const std::vector<const char*>& send, const std::ve
         }
     }
     rccl_check(ncclGroupEnd(), "ncclGroupEnd");
+}
+
+bool exchange_pairs_sparse(Graph& g, const std::vector<const unsigned long long*>& counts, int64_t dense_local, int words,
+                           const std::function<std::pair<const char*, char*>(size_t, PairOffsets, PairOffsets)>& prepare,
+                           const std::function<void(size_t, int64_t)>& consume, int64_t* vol) {
+    const int P = g.P;
+    const size_t ns = g.shards.size(), PP = (size_t)P * P;
+    // row r of the P x P matrix: shard r's pairs per peer (only r's rank fills it); last cell: the dense volume
+    std::vector<int64_t> mat(PP + 1, 0);
+    for (size_t i = 0; i < ns; ++i) {  // (the device's uint64 counts are read as int64: same size, never negative)
+        Shard& sh = *g.shards[i];
+        DeviceGuard dg(sh);
+        copy_d2h(&mat[(size_t)sh.index * P], counts[i], (size_t)P * sizeof(unsigned long long), sh.stream);
+    }
+    mat[PP] = dense_local;
+    allreduce_sum_i64(g, mat.data(), P * P + 1);  // summed over ranks: every rank takes the same decision
+    int64_t pairs = 0;
+    for (size_t k = 0; k < PP; ++k) pairs += mat[k];
+    if (vol) vol[0] = pairs, vol[1] = mat[PP];
+    if (2 * pairs >= mat[PP]) return false;
+    std::vector<const char*> sp(ns);
+    std::vector<char*> rp(ns);
+    std::vector<std::vector<int64_t>> so(ns, std::vector<int64_t>((size_t)P + 1, 0)), ro = so;
+    std::vector<std::vector<int64_t>> sc(ns, std::vector<int64_t>((size_t)P, 0)), rc = sc;
+    for (size_t i = 0; i < ns; ++i) {
+        Shard& sh = *g.shards[i];
+        DeviceGuard dg(sh);
+        for (int q = 0; q < P; ++q) {
+            so[i][(size_t)q + 1] = so[i][(size_t)q] + (sc[i][(size_t)q] = mat[(size_t)sh.index * P + q]);
+            ro[i][(size_t)q + 1] = ro[i][(size_t)q] + (rc[i][(size_t)q] = mat[(size_t)q * P + sh.index]);
+        }
+        std::tie(sp[i], rp[i]) = prepare(i, so[i], ro[i]);
+        for (auto* a : {&so[i], &ro[i], &sc[i], &rc[i]})  // pairs -> uint64 elements
+            for (int64_t& x : *a) x *= words;
+    }
+    exchange_runs(g, sp, so, sc, rp, ro, rc, sizeof(unsigned long long), ncclUint64);
+    for (size_t i = 0; i < ns; ++i) {
+        DeviceGuard dg(*g.shards[i]);
+        if (ro[i][(size_t)P] > 0) consume(i, ro[i][(size_t)P] / words);
+    }
+    return true;
 }
 
 void exchange_vec(Graph& g, uint32_t adj, std::vector<void*>& bufs, size_t elem_bytes, ncclDataType_t type) {

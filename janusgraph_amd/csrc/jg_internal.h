@@ -446,13 +446,17 @@ void exchange_halo_reverse(Graph& g, uint32_t adj, std::vector<void*>& vecs, std
 // lists -> segments; reverse: segments -> the owners' send-list words.
 void exchange_halo_bits(Graph& g, uint32_t adj, std::vector<uint64_t*>& sends, std::vector<uint64_t*>& bitmaps,
                         bool reverse);
-// Per-peer runs whose lengths both sides know (the sparse reverse exchange of the sharded bit-parallel
-// BFS): local shard i sends scount[i][q] elements from send[i] + soff[i][q] to peer q and receives
-// rcount[i][q] elements from q at recv[i] + roff[i][q] (offsets and counts in elements of eb bytes).
-void exchange_runs(Graph& g, const std::vector<const char*>& send, const std::vector<std::vector<int64_t>>& soff,
-                   const std::vector<std::vector<int64_t>>& scount, const std::vector<char*>& recv,
-                   const std::vector<std::vector<int64_t>>& roff, const std::vector<std::vector<int64_t>>& rcount,
-                   size_t eb, ncclDataType_t type);
+// One sparse pair exchange (sharded CC's label rounds, the sharded 64-source BFS's top-down levels): pairs
+// of `words` uint64 each go to their peers in per-peer runs when that moves less than the dense exchange.
+// counts[i]: local shard i's P per-peer pair counts, on its device; dense_local: the dense volume of the
+// local shards.  Both are summed over ranks in one all-reduce, so every rank decides alike: false (nothing
+// sent, no callback ran) when 2 * pairs >= dense.  Else, per shard under its guard, prepare(i, soff, roff) gets
+// the [P + 1] offsets in pairs of what shard i sends to and receives from each peer, packs, and returns the send and
+// receive buffers; then consume(i, n) gets the n > 0 pairs shard i received.  vol[2]: summed pairs and dense volume.
+using PairOffsets = const std::vector<int64_t>&;
+bool exchange_pairs_sparse(Graph& g, const std::vector<const unsigned long long*>& counts, int64_t dense_local, int words,
+                           const std::function<std::pair<const char*, char*>(size_t, PairOffsets, PairOffsets)>& prepare,
+                           const std::function<void(size_t, int64_t)>& consume, int64_t* vol = nullptr);
 // Both directions of exchange_halo_bits in one grouped step (the sharded DO-BFS, whose level direction is
 // decided on the device): forward fsend -> fbitmap segments, and reverse rbitmap segments -> rsend.
 void exchange_halo_bits_both(Graph& g, uint32_t adj, std::vector<uint64_t*>& fsend, std::vector<uint64_t*>& fbitmap,

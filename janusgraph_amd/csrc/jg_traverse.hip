@@ -3136,78 +3136,47 @@ private:
     // the sources set a few thousand).  Returns whether it ran (otherwise the dense exchange does).
     bool reverse_exchange_sparse() {
         const int P = g.P;
-        const size_t ns_ = sv.size();
-        std::vector<std::vector<int64_t>> cnt(ns_, std::vector<int64_t>((size_t)P, 0));
-        std::vector<int64_t> mat((size_t)P * P + 1, 0);
-        for (size_t i = 0; i < ns_; ++i) {
-            Shard& sh = *sv[i].sh;
-            DeviceGuard dg(sh);
-            // per-peer slot counts: the top-down kernel counted the slots it set first
-            std::vector<unsigned long long> c((size_t)P);
-            copy_d2h(c.data(), sv[i].pcnt.get(), (size_t)P * sizeof(unsigned long long), sh.stream);
-            for (int q = 0; q < P; ++q) {
-                cnt[i][(size_t)q] = (int64_t)c[(size_t)q];
-                mat[(size_t)sh.index * P + q] = (int64_t)c[(size_t)q];
-            }
-            mat[(size_t)P * P] += sh.halo_both.recv_off[(size_t)P];  // the dense exchange's words
-        }
-        allreduce_sum_i64(g, mat.data(), P * P + 1);
-        int64_t pairs_all = 0;
-        for (int64_t k = 0; k < (int64_t)P * P; ++k) pairs_all += mat[(size_t)k];
-        if (2 * pairs_all >= mat[(size_t)P * P]) return false;
-        std::vector<const char*> sp(ns_);
-        std::vector<char*> rp(ns_);
-        std::vector<std::vector<int64_t>> so(ns_), sc(ns_), ro(ns_), rc(ns_);
-        for (size_t i = 0; i < ns_; ++i) {
-            MsBfsShard& s = sv[i];
-            Shard& sh = *s.sh;
-            DeviceGuard dg(sh);
-            so[i].assign((size_t)P + 1, 0);
-            ro[i].assign((size_t)P + 1, 0);
-            sc[i].assign((size_t)P, 0);
-            rc[i].assign((size_t)P, 0);
-            PairRuns pk{}, pv{};
-            pk.P = pv.P = P;
-            for (int q = 0; q < P; ++q) {
-                so[i][(size_t)q + 1] = so[i][(size_t)q] + cnt[i][(size_t)q];
-                const int64_t from_q = mat[(size_t)q * P + sh.index];
-                ro[i][(size_t)q + 1] = ro[i][(size_t)q] + from_q;
-                sc[i][(size_t)q] = 2 * cnt[i][(size_t)q];  // uint64 elements: two per pair
-                rc[i][(size_t)q] = 2 * from_q;
-            }
-            for (int q = 0; q <= P; ++q) {
-                pk.off[q] = so[i][(size_t)q];
-                pv.off[q] = ro[i][(size_t)q];
-                pv.send_off[q] = sh.halo_both.send_off[(size_t)q];
-            }
-            const int64_t nh = so[i][(size_t)P];
-            if (nh > 0) {
-                msbfs_pair_pack_kernel<<<(unsigned)kRedBlocks, kRedThreads, 0, sh.stream>>>(
-                    s.hlist.get(), nh, s.hs.get(), sh.halo_both.tbits, sh.index, pk, s.bcount.get(), s.pairs.get());
-                JG_LAUNCH_CHECK();
-            }
-            for (int q = 0; q <= P; ++q) {
-                so[i][(size_t)q] *= 2;
-                ro[i][(size_t)q] *= 2;
-            }
-            sp[i] = reinterpret_cast<const char*>(s.pairs.get());
-            rp[i] = reinterpret_cast<char*>(s.rpairs.get());
-            s.nrp = ro[i][(size_t)P] / 2;
-            s.pv = pv;
-        }
-        exchange_runs(g, sp, so, sc, rp, ro, rc, sizeof(unsigned long long), ncclUint64);
+        std::vector<const unsigned long long*> counts;  // the top-down kernel counted the slots it set first
+        int64_t vol[2], dense = 0;                      // pairs and the dense exchange's words, all ranks / local
         each([&](MsBfsShard& s) {
-            if (s.nrp > 0) {
+            counts.push_back(s.pcnt.get());
+            dense += s.sh->halo_both.recv_off[(size_t)P];
+        });
+        const bool ran = exchange_pairs_sparse(
+            g, counts, dense, 2,  // uint64 elements: two per pair
+            [&](size_t i, const std::vector<int64_t>& so, const std::vector<int64_t>& ro) {
+                MsBfsShard& s = sv[i];
+                Shard& sh = *s.sh;
+                PairRuns pk{}, pv{};
+                pk.P = pv.P = P;
+                for (int q = 0; q <= P; ++q) {
+                    pk.off[q] = so[(size_t)q];
+                    pv.off[q] = ro[(size_t)q];
+                    pv.send_off[q] = sh.halo_both.send_off[(size_t)q];
+                }
+                const int64_t nh = so[(size_t)P];
+                if (nh > 0) {
+                    msbfs_pair_pack_kernel<<<(unsigned)kRedBlocks, kRedThreads, 0, sh.stream>>>(
+                        s.hlist.get(), nh, s.hs.get(), sh.halo_both.tbits, sh.index, pk, s.bcount.get(), s.pairs.get());
+                    JG_LAUNCH_CHECK();
+                }
+                s.nrp = ro[(size_t)P];
+                s.pv = pv;
+                return std::make_pair(reinterpret_cast<const char*>(s.pairs.get()),
+                                      reinterpret_cast<char*>(s.rpairs.get()));
+            },
+            [&](size_t i, int64_t) {
+                MsBfsShard& s = sv[i];
                 msbfs_td_recv_pairs_kernel<<<grid_for(s.nrp), kBlock, 0, s.sh->stream>>>(
                     s.rpairs.get(), s.nrp, s.pv, s.sh->halo_both.send_src.get(), s.vis.get(), s.F[cur ^ 1].get(),
                     s.touched.get(), s.touched_off.get(), s.ctr.get() + 1);
                 JG_LAUNCH_CHECK();
-            }
-        });
-        if (debug_bfs())
+            },
+            vol);
+        if (ran && debug_bfs())
             std::fprintf(stderr, "[jg msbfs] level %d top-down, sparse reverse exchange: %lld pairs (dense: %lld words)\n",
-                         level, (long long)pairs_all, (long long)mat[(size_t)P * P]);
-        return true;
+                         level, (long long)vol[0], (long long)vol[1]);
+        return ran;
     }
 
     // the peers' halo slots for every own row (fv: the staging vectors, rv: the receive buffers)

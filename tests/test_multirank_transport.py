@@ -34,6 +34,49 @@ def _combine(dist, world, a, fill):
     return out, owned
 
 
+def _log_to(path, switch):
+    """The library's debug log (stderr) into `path`.  The switch is read once per process, so it is set,
+    and fd 2 redirected, before the library loads."""
+    os.environ[switch] = "1"
+    os.dup2(os.open(path, os.O_WRONLY | os.O_CREAT | os.O_APPEND), 2)
+
+
+_MARK = "\n#### jg test pass: "
+
+
+def _mark(name):
+    os.write(2, f"{_MARK}{name}\n".encode())
+
+
+def _passes(path):
+    """The log of each marked pass: {name: text}."""
+    with open(path) as f:
+        parts = f.read().split(_MARK)[1:]
+    return {p.split("\n", 1)[0]: p.split("\n", 1)[1] for p in parts}
+
+
+def _chains_graph():
+    """80 chains of 40 vertices with scattered ids, and a random part (small components and a few larger
+    ones): many label rounds, few labels moving in each after the first."""
+    rng = np.random.default_rng(5)
+    n, plen = 4000, 40
+    perm = rng.permutation(n)
+    s, d = [], []
+    for c0 in range(0, 3200, plen):
+        ch = perm[c0:c0 + plen]
+        s += list(ch[:-1])
+        d += list(ch[1:])
+    s += list(rng.integers(3200, n, 900))
+    d += list(rng.integers(3200, n, 900))
+    return n, np.array(s, np.int32), np.array(d, np.int32), (np.arange(n, dtype=np.int64) + 3) * 7
+
+
+def _msbfs_sources(deg):
+    """62 sources with an edge, an isolated vertex and a hub."""
+    return np.concatenate([np.random.default_rng(14).choice(np.flatnonzero(deg > 0), 62, replace=False),
+                           [np.flatnonzero(deg == 0)[0], int(np.argmax(deg))]]).astype(np.int64)
+
+
 def _worker(rank, world, port, halo, errfile):
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -100,13 +143,14 @@ def _worker(rank, world, port, halo, errfile):
         raise
 
 
-def _worker_msbfs(rank, world, port, errfile):
+def _worker_msbfs(rank, world, port, errfile, logfile):
     """64 sources, unbounded, rank mode (the driver's N-GPU bench runs this path): top-down levels with the
-    sparse pair exchange, pull levels after the frontier's peak, the last levels top-down again; every row
-    against the oracle, and the level count."""
+    sparse pair exchange (the library's JG_DEBUG_BFS log must show it), pull levels after the frontier's peak,
+    the last levels top-down again; every row against the oracle, and the level count."""
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"
         os.environ["MASTER_PORT"] = str(port)
+        _log_to(f"{logfile}.{rank}", "JG_DEBUG_BFS")
         sys.path.insert(0, ROOT)
         import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -121,10 +165,9 @@ def _worker_msbfs(rank, world, port, errfile):
         ctx = jg.Context((0,), rank=rank, nranks=world, transport=GlooTransport(dist, world))
         g = ctx.build(vid, vid[s], vid[d], flags=jg.ADJ_BOTH)
         deg = np.bincount(ds, minlength=n) + np.bincount(dd, minlength=n)
-        # 62 sources with an edge, an isolated vertex and a hub
-        srcs = np.concatenate([np.random.default_rng(14).choice(np.flatnonzero(deg > 0), 62, replace=False),
-                               [np.flatnonzero(deg == 0)[0], int(np.argmax(deg))]]).astype(np.int64)
+        srcs = _msbfs_sources(deg)
         for max_depth in (-1, 2):
+            _mark(f"max_depth {max_depth}")
             got = g.bfs(vid[srcs], jg.DIR_BOTH, max_depth=max_depth)
             levels = ctx.stats()["levels"]
             got, own = _combine(dist, world, got.ravel(), np.iinfo(np.int32).min)
@@ -155,9 +198,7 @@ def _worker_cc(rank, world, port, errfile, logfile):
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"
         os.environ["MASTER_PORT"] = str(port)
-        os.environ["JG_DEBUG_CC"] = "1"
-        fd = os.open(f"{logfile}.{rank}", os.O_WRONLY | os.O_CREAT | os.O_TRUNC)
-        os.dup2(fd, 2)  # the library's per-round log
+        _log_to(f"{logfile}.{rank}", "JG_DEBUG_CC")
         sys.path.insert(0, ROOT)
         import torch.distributed as dist
         dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -165,23 +206,13 @@ def _worker_cc(rank, world, port, errfile, logfile):
         from janusgraph_amd import _lib
         from janusgraph_amd.transport import GlooTransport
         from oracle import oracle as o
-        rng = np.random.default_rng(5)
-        n, plen = 4000, 40
-        perm = rng.permutation(n)
-        s, d = [], []
-        for c0 in range(0, 3200, plen):  # 80 chains of 40 vertices with scattered ids
-            ch = perm[c0:c0 + plen]
-            s += list(ch[:-1])
-            d += list(ch[1:])
-        s += list(rng.integers(3200, n, 900))  # a random part: small components and a few larger ones
-        d += list(rng.integers(3200, n, 900))
-        s, d = np.array(s, np.int32), np.array(d, np.int32)
-        vid = (np.arange(n, dtype=np.int64) + 3) * 7
+        n, s, d, vid = _chains_graph()
         ctx = jg.Context((0,), rank=rank, nranks=world, transport=GlooTransport(dist, world))
         g = ctx.build(vid, vid[s], vid[d], flags=jg.ADJ_BOTH)
         out = []
         for sparse in (1, 0):
             _lib.tune_set("cc_sparse", sparse)
+            _mark(f"cc_sparse {sparse}")
             comp, it = g.connected_components()
             comp, own = _combine(dist, world, comp, np.iinfo(np.int64).max)
             out.append((comp, it, own))
@@ -203,20 +234,64 @@ def _worker_cc(rank, world, port, errfile, logfile):
         raise
 
 
+def _worker_logical(errfile, logfile):
+    """Three logical shards in one process (exchange_runs' device-copy branch, which rank mode never takes):
+    the chains graph through sharded CC, sparse and dense rounds, and RMAT-13 through the 64-source BFS,
+    both against the oracle, with both debug logs."""
+    try:
+        os.environ["JG_DEBUG_BFS"] = "1"
+        _log_to(logfile, "JG_DEBUG_CC")
+        sys.path.insert(0, ROOT)
+        import janusgraph_amd as jg
+        from janusgraph_amd import _lib
+        from oracle import oracle as o
+        ctx = jg.Context((0,) * 3)
+        n, s, d, vid = _chains_graph()
+        g = ctx.build(vid, vid[s], vid[d], flags=jg.ADJ_BOTH)
+        assert g.info()["num_shards"] == 3
+        cref, cit = o.connected_components(n, s, d, vid)
+        for sparse in (1, 0):
+            _lib.tune_set("cc_sparse", sparse)
+            _mark(f"cc_sparse {sparse}")
+            comp, it = g.connected_components()
+            np.testing.assert_array_equal(comp, cref)
+            assert it == cit, (it, cit)
+        _lib.tune_set("cc_sparse", 1)
+        g.close()
+        scale = 13
+        n = 1 << scale
+        s, d = o.rmat_edges(scale, 16, 0x5EED + scale)
+        ds, dd = s.astype(np.int32), d.astype(np.int32)
+        vid = (np.arange(n, dtype=np.int64) + 1) << 8
+        g = ctx.build(vid, vid[s], vid[d], flags=jg.ADJ_BOTH)
+        srcs = _msbfs_sources(np.bincount(ds, minlength=n) + np.bincount(dd, minlength=n))
+        _mark("msbfs")
+        got = g.bfs(vid[srcs], jg.DIR_BOTH)
+        ptr, adj = o.csr_unordered(n, ds, dd, both=True)
+        np.testing.assert_array_equal(got, o.msbfs_csr(n, ptr, adj, srcs, -1))
+        g.close()
+        ctx.close()
+    except BaseException:
+        import traceback
+        with open(errfile, "a") as f:
+            f.write(traceback.format_exc())
+        raise
+
+
 def _free_port():
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         return sk.getsockname()[1]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("world,halo", [(2, 1), (2, 0), (3, 1)])
-def test_ranks_over_host_transport(tmp_path, world, halo):
+def _run(tmp_path, target, world, args):
+    """One spawned process per rank, target(rank, world, port, *args(errfile, logfile)); returns the log
+    file's stem (rank r writes `stem.r`)."""
     import multiprocessing as mp
     ctx = mp.get_context("spawn")
-    errfile = str(tmp_path / "err.txt")
+    errfile, logfile = str(tmp_path / "err.txt"), str(tmp_path / "lib.log")
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, halo, errfile)) for r in range(world)]
+    procs = [ctx.Process(target=target, args=(r, world, port) + args(errfile, logfile)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
@@ -226,44 +301,52 @@ def test_ranks_over_host_transport(tmp_path, world, halo):
             p.kill()
     err = open(errfile).read() if os.path.exists(errfile) else ""
     assert all(p.exitcode == 0 for p in procs), f"exit codes {[p.exitcode for p in procs]}\n{err}"
+    return logfile
+
+
+def _check_cc_log(cc):
+    """The chains graph's later rounds go sparse in both directions (on 2 ranks from round 3, on 3 ranks or
+    shards from round 4; which round and how many pairs depends on link order and is not asserted); the
+    cc_sparse 0 pass logs dense rounds only."""
+    on, off = ("\n".join(ln for ln in cc[f"cc_sparse {k}"].splitlines() if ln.startswith("[jg cc] round")) for k in (1, 0))
+    assert "forward sparse" in on, on[-2000:]
+    assert "reverse sparse" in on, on[-2000:]
+    assert "forward dense" in off and "sparse" not in off, off[-2000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world,halo", [(2, 1), (2, 0), (3, 1)])
+def test_ranks_over_host_transport(tmp_path, world, halo):
+    _run(tmp_path, _worker, world, lambda errfile, logfile: (halo, errfile))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 3])
 def test_msbfs64_unbounded_ranks_over_host_transport(tmp_path, world):
-    import multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    errfile = str(tmp_path / "err.txt")
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_msbfs, args=(r, world, port, errfile)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(240)
-    for p in procs:
-        if p.is_alive():
-            p.kill()
-    err = open(errfile).read() if os.path.exists(errfile) else ""
-    assert all(p.exitcode == 0 for p in procs), f"exit codes {[p.exitcode for p in procs]}\n{err}"
+    logfile = _run(tmp_path, _worker_msbfs, world, lambda errfile, logfile: (errfile, logfile))
+    log = _passes(f"{logfile}.0")
+    assert "sparse reverse exchange" in log["max_depth -1"], log["max_depth -1"][-2000:]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_cc_sparse_rounds_ranks_over_host_transport(tmp_path, world):
+    logfile = _run(tmp_path, _worker_cc, world, lambda errfile, logfile: (errfile, logfile))
+    _check_cc_log(_passes(f"{logfile}.0"))
+
+
+@pytest.mark.gpu
+def test_sparse_exchanges_logical_shards(tmp_path):
     import multiprocessing as mp
-    ctx = mp.get_context("spawn")
-    errfile = str(tmp_path / "err.txt")
-    logfile = str(tmp_path / "cc.log")
-    port = _free_port()
-    procs = [ctx.Process(target=_worker_cc, args=(r, world, port, errfile, logfile)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(240)
-    for p in procs:
-        if p.is_alive():
-            p.kill()
+    errfile, logfile = str(tmp_path / "err.txt"), str(tmp_path / "lib.log")
+    p = mp.get_context("spawn").Process(target=_worker_logical, args=(errfile, logfile))
+    p.start()
+    p.join(240)
+    if p.is_alive():
+        p.kill()
     err = open(errfile).read() if os.path.exists(errfile) else ""
-    assert all(p.exitcode == 0 for p in procs), f"exit codes {[p.exitcode for p in procs]}\n{err}"
-    log = open(f"{logfile}.0").read()
-    assert "forward sparse" in log, log[-2000:]
+    assert p.exitcode == 0, f"exit code {p.exitcode}\n{err}"
+    log = _passes(logfile)
+    _check_cc_log(log)
+    assert "sparse reverse exchange" in log["msbfs"], log["msbfs"][-2000:]
+
