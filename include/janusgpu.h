@@ -83,7 +83,9 @@ extern "C" {
  * jg_sssp_kept_dag, jg_sssp_kept_dag_read added; JG_ADJ_EDGE_INDEX, jg_graph_neighbor_edges,
  * jg_bfs_kept_dag_edges, jg_bfs_kept_dag_read_edges, jg_sssp_kept_dag_edges, jg_sssp_kept_dag_read_edges added;
  * jg_graph_set_weights_f64, jg_sssp_keep_f64, jg_sssp_kept_row_f64, jg_sssp_kept_dag_f64,
- * jg_sssp_kept_dag_edges_f64, jg_sssp_kept_dag_read_f64 added. */
+ * jg_sssp_kept_dag_edges_f64, jg_sssp_kept_dag_read_f64 added; jg_builder_keep_relations,
+ * jg_builder_set_weight_key_f64, jg_graph_edge_relations, jg_bfs_kept_dag_read_relations,
+ * jg_sssp_kept_dag_read_relations added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -110,8 +112,11 @@ extern "C" {
  * BOTH both entries of an edge carry its ordinal (a self-loop: two entries of one row).  Inside a run of equal
  * neighbours of a row, ordinals ascend.  Read back by jg_graph_neighbor_edges and listed by the edge-listing
  * predecessor DAGs (jg_bfs_kept_dag_edges, jg_sssp_kept_dag_edges).
+ * A jg_builder_add_rows builder that opted in (jg_builder_keep_relations or jg_builder_set_weight_key_f64) numbers
+ * the decoder's kept list instead: every visible OUT user edge of a kept row, in chunk order then entry order,
+ * ghost-ended edges included.
  * JG_ERR_UNSUPPORTED with the flag: graphs of several shards (logical shards, rank mode); jg_builder_add_rows
- * builders and jg_graph_build_edgestore (the relation ids the decoder computes are not kept);
+ * builders without such an opt-in and jg_graph_build_edgestore (the relation ids the decoder computes are not kept);
  * jg_builder_finish_labels (its select compacts the list); jg_graph_build_rmat (no caller edge list).
  * Without the flag a build is what it was before the flag existed: no allocation, no sort payload, no launch. */
 #define JG_ADJ_EDGE_INDEX 16u
@@ -297,6 +302,49 @@ int jg_builder_set_query_limit(jg_builder* b, int64_t limit, int32_t in_entries)
 #define JG_PROP_STRING 11
 int jg_builder_set_weight_key(jg_builder* b, int64_t weight_key, const int64_t* key_ids, const int8_t* key_types,
                               int32_t nkeys);
+/* ---- edge identity and fp64 weights from rows ----
+ * Both are opt-in: a rows builder that calls neither behaves as before (JG_ADJ_EDGE_INDEX: JG_ERR_UNSUPPORTED).
+ *
+ * jg_builder_keep_relations: the decoder keeps each kept edge's JanusGraph relation id (the id
+ * EdgeSerializer.parseRelation reads beside the other vertex; what the Java side detaches an Edge by) aligned
+ * with the edge list.  Must precede every chunk (else JG_ERR_STATE); rows only (jg_builder_add_vertices /
+ * _add_edges / _add_labeled_edges on such a builder: JG_ERR_ARG); mutually exclusive with a positive
+ * jg_builder_set_query_limit, in either order (the second of the two: JG_ERR_STATE); may be combined with
+ * jg_builder_keep_labels (jg_builder_finish_labels keeps refusing JG_ADJ_EDGE_INDEX).
+ * jg_builder_finish(flags | JG_ADJ_EDGE_INDEX) then succeeds on one shard (several shards, rank mode:
+ * JG_ERR_UNSUPPORTED).  The graph's edge list is the decoder's kept list (see JG_ADJ_EDGE_INDEX), ordinals index
+ * it, and the relation table (8 B per listed edge, counted in jg_graph_info.device_bytes) moves into the graph.
+ * Finished without the flag, the table is dropped and the graph is the plain one.
+ *
+ * jg_graph_edge_relations: rel_out[i] = the relation id of edge ordinal ordinals[i], gathered on the device.
+ * A graph without the table (built from ids, or without the opt-in and the flag): JG_ERR_UNSUPPORTED; an ordinal
+ * >= the list length: JG_ERR_ARG (checked on the device; nothing out of range is read); count == 0: JG_OK.
+ * jg_bfs_kept_dag_read_relations / jg_sssp_kept_dag_read_relations (the latter for the integer and the f64
+ * edge-listing DAG): the relation ids of entries [off[first], off[first + count]) of the held edge-listing DAG,
+ * parallel to pred_out: one device gather through the held ordinals, one copy out.  Errors as for the
+ * _read_edges pair, plus JG_ERR_UNSUPPORTED without the table.
+ *
+ * jg_builder_set_weight_key_f64: arguments and call rules of jg_builder_set_weight_key; setting both weight keys
+ * on one builder is JG_ERR_STATE.  The weight key's type decides how its value is read, one double per edge:
+ *   JG_PROP_DOUBLE  8 bytes, the big-endian IEEE bits (DoubleSerializer.write);
+ *   JG_PROP_LONG    8 bytes, big-endian value - Long.MIN_VALUE (LongSerializer), converted exactly;
+ *   JG_PROP_INT     a signed VariableLong, converted exactly;
+ *   JG_PROP_FLOAT (TinkerPop adds Floats in binary32), any other type, or a key absent from the table:
+ *   JG_ERR_UNSUPPORTED from this call.
+ * An integer value with |v| > 2^53 fails its chunk's completion with JG_ERR_UNSUPPORTED; a value cut short by its
+ * entry's end is a malformed entry (JG_ERR_ARG).  An edge without the property or with a null value gets NaN.
+ * The builder must be finished with JG_ADJ_EDGE_INDEX (without: JG_ERR_ARG), which this call permits on its own;
+ * the finish then does what jg_graph_set_weights_f64 does on the same values (statistics, gate, automatic delta
+ * and error codes: a NaN, zero, negative or infinite weight anywhere in the list JG_ERR_ARG, an absorbing range
+ * JG_ERR_UNSUPPORTED).  A failed finish builds no graph and leaves the builder destroyable.  Afterwards
+ * jg_sssp_keep_f64 and the _f64 DAG calls work as on an ids graph, and a later jg_graph_set_weights_f64 (m = the
+ * list length) replaces the weights.  JG_ADJ_WEIGHT_BOTH is not needed and its rule is unchanged. */
+int jg_builder_keep_relations(jg_builder* b);
+int jg_builder_set_weight_key_f64(jg_builder* b, int64_t weight_key, const int64_t* key_ids, const int8_t* key_types,
+                                  int32_t nkeys);
+int jg_graph_edge_relations(const jg_graph* g, const uint32_t* ordinals, int64_t count, int64_t* rel_out);
+int jg_bfs_kept_dag_read_relations(jg_graph* g, int64_t first, int64_t count, int64_t* rel_out);
+int jg_sssp_kept_dag_read_relations(jg_graph* g, int64_t first, int64_t count, int64_t* rel_out);
 int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out);
 /* ---- label-scoped graphs (typed message scopes) ----
  * Fulgora turns each MessageScope.Local of a program into a vertex-centric query

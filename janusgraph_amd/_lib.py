@@ -57,6 +57,8 @@ EXPORTS = [
     "jg_sssp_kept_dag_read_edges",
     "jg_graph_set_weights_f64", "jg_sssp_keep_f64", "jg_sssp_kept_row_f64", "jg_sssp_kept_dag_f64",
     "jg_sssp_kept_dag_edges_f64", "jg_sssp_kept_dag_read_f64",
+    "jg_builder_keep_relations", "jg_builder_set_weight_key_f64", "jg_graph_edge_relations",
+    "jg_bfs_kept_dag_read_relations", "jg_sssp_kept_dag_read_relations",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -229,6 +231,11 @@ def load():
         "jg_sssp_kept_dag_edges": ([_P, _P, _i64, _P, _P, _P], ctypes.c_int),
         "jg_sssp_kept_dag_read_edges": ([_P, _i64, _i64, _P], ctypes.c_int),
         "jg_graph_set_weights_f64": ([_P, _P, _i64], ctypes.c_int),
+        "jg_builder_keep_relations": ([_P], ctypes.c_int),
+        "jg_builder_set_weight_key_f64": ([_P, _i64, _P, _P, _i32], ctypes.c_int),
+        "jg_graph_edge_relations": ([_P, _P, _i64, _P], ctypes.c_int),
+        "jg_bfs_kept_dag_read_relations": ([_P, _i64, _i64, _P], ctypes.c_int),
+        "jg_sssp_kept_dag_read_relations": ([_P, _i64, _i64, _P], ctypes.c_int),
         "jg_sssp_keep_f64": ([_P, _i64, _i32], ctypes.c_int),
         "jg_sssp_kept_row_f64": ([_P, _P], ctypes.c_int),
         "jg_sssp_kept_dag_f64": ([_P, _P, ctypes.c_double, _P, _P, _P], ctypes.c_int),
@@ -441,6 +448,12 @@ class Builder:
         positive query limit)."""
         check(load().jg_builder_keep_labels(self._h))
 
+    def keep_relations(self):
+        """jg_builder_keep_relations: keep the JanusGraph relation id beside every edge decoded from the rows
+        (before the first chunk; rows only; not under a positive query limit).  finish(flags | ADJ_EDGE_INDEX)
+        then numbers the decoder's edge list and Graph.edge_relations names each ordinal's relation."""
+        check(load().jg_builder_keep_relations(self._h))
+
     def add_edges(self, src, dst, weight=None, label=None):
         """jg_builder_add_edges, or with `label` (one int64 per edge) jg_builder_add_labeled_edges."""
         src = np.ascontiguousarray(src, np.int64)
@@ -481,6 +494,16 @@ class Builder:
         if len(ids) != len(types):
             raise ValueError("key_ids and key_types differ in length")
         check(load().jg_builder_set_weight_key(self._h, int(weight_key), _ptr(ids), _ptr(types), len(ids)))
+
+    def set_weight_key_f64(self, weight_key, key_ids=(), key_types=()):
+        """jg_builder_set_weight_key_f64: the edges' Double (or Integer / Long) weight decoded on the GPU as one
+        float64 per edge; arguments as set_weight_key.  The builder must be finished with ADJ_EDGE_INDEX, and the
+        graph then holds the weights as after Graph.set_weights_f64 of the same values."""
+        ids = np.ascontiguousarray(key_ids, np.int64)
+        types = np.ascontiguousarray(key_types, np.int8)
+        if len(ids) != len(types):
+            raise ValueError("key_ids and key_types differ in length")
+        check(load().jg_builder_set_weight_key_f64(self._h, int(weight_key), _ptr(ids), _ptr(types), len(ids)))
 
     def add_rows(self, row_keys, row_entry_off, data, entry_off, value_pos, entry_weight=None):
         keys = np.ascontiguousarray(row_keys, np.uint64)
@@ -677,20 +700,20 @@ class Graph:
             pred = pred[:k]
         return vertex[:count], value[:count], off, pred
 
-    def _dag_read_edges(self, read_fn, read_edges_fn, first, count, entries):
-        """The edge ordinals of entries [off[first], off[first + count]) of the held edge-listing DAG that read_fn
-        and read_edges_fn read (`entries`: their number, when the caller knows it)."""
+    def _dag_read_edges(self, read_fn, read_edges_fn, first, count, entries, dtype=np.uint32):
+        """The edge ordinals (dtype int64: the relation ids) of entries [off[first], off[first + count]) of the held
+        edge-listing DAG that read_fn and read_edges_fn read (`entries`: their number, when the caller knows it)."""
         if entries is None:
             off = np.empty(count + 1, np.int64)
             check(read_fn(self._h, int(first), int(count), None, None, _ptr(off), None))
             entries = int(off[-1] - off[0])
-        edge = np.empty(max(entries, 1), np.uint32)
+        edge = np.empty(max(entries, 1), dtype)
         check(read_edges_fn(self._h, int(first), int(count), _ptr(edge)))
         return edge[:entries]
 
-    def _dag_whole(self, read, read_edges, raw_read_fn, nv, ne):
-        """(vertex, value, off, pred) of a held DAG of nv vertices and ne entries, and its edge ordinals after them
-        when read_edges is not None.  read / read_edges: the family's public readers, raw_read_fn: the library's.
+    def _dag_whole(self, read, read_edges, raw_read_fn, nv, ne, edge_dtype=np.uint32):
+        """(vertex, value, off, pred) of a held DAG of nv vertices and ne entries, and its edge ordinals (or, from a
+        relation reader with edge_dtype int64, its relation ids) after them when read_edges is not None.  read / read_edges: the family's public readers, raw_read_fn: the library's.
         More than DAG_READ_ENTRIES entries are read in vertex ranges of at most that many (a vertex with more is
         read alone), each range straight into its place."""
         if ne <= self.DAG_READ_ENTRIES:
@@ -698,7 +721,7 @@ class Graph:
             return whole if read_edges is None else whole + (read_edges(0, nv, ne),)
         vertex, value, off, _ = read(0, nv, want_pred=False)
         pred = np.empty(ne, np.int32)
-        edge = None if read_edges is None else np.empty(ne, np.uint32)
+        edge = None if read_edges is None else np.empty(ne, edge_dtype)
         first = 0
         while first < nv:
             last = int(np.searchsorted(off, off[first] + self.DAG_READ_ENTRIES, side="right")) - 1
@@ -748,6 +771,18 @@ class Graph:
         return self._dag_whole(self.bfs_kept_dag_read, self.bfs_kept_dag_read_edges, load().jg_bfs_kept_dag_read,
                                nv, ne)
 
+    def bfs_kept_dag_read_relations(self, first, count, entries=None):
+        """jg_bfs_kept_dag_read_relations: the relation ids (int64) of the held edge-listing DAG's entries
+        [off[first], off[first + count]), gathered on the device (the graph needs Builder.keep_relations)."""
+        return self._dag_read_edges(load().jg_bfs_kept_dag_read, load().jg_bfs_kept_dag_read_relations, first, count,
+                                    entries, np.int64)
+
+    def bfs_kept_dag_relations(self, s, target=None):
+        """bfs_kept_dag_edges with relation ids in place of ordinals: (vertex, depth, off, pred, rel)."""
+        nv, ne, _ = self.bfs_kept_dag_edges_build(s, target)
+        return self._dag_whole(self.bfs_kept_dag_read, self.bfs_kept_dag_read_relations, load().jg_bfs_kept_dag_read,
+                               nv, ne, np.int64)
+
     def sssp_kept_dag_edges_build(self, target=None, max_distance=-1):
         """jg_sssp_kept_dag_edges: as sssp_kept_dag_build, for the edge-listing DAG (one entry per tight
         adjacency entry; the graph needs ADJ_EDGE_INDEX).  It replaces a held sssp_kept_dag DAG."""
@@ -764,6 +799,17 @@ class Graph:
         nv, ne, _ = self.sssp_kept_dag_edges_build(target, max_distance)
         return self._dag_whole(self.sssp_kept_dag_read, self.sssp_kept_dag_read_edges, load().jg_sssp_kept_dag_read,
                                nv, ne)
+
+    def sssp_kept_dag_read_relations(self, first, count, entries=None):
+        """jg_sssp_kept_dag_read_relations, as bfs_kept_dag_read_relations (integer and f64 edge-listing DAGs)."""
+        return self._dag_read_edges(load().jg_sssp_kept_dag_read, load().jg_sssp_kept_dag_read_relations, first,
+                                    count, entries, np.int64)
+
+    def sssp_kept_dag_relations(self, target=None, max_distance=-1):
+        """sssp_kept_dag_edges with relation ids in place of ordinals: (vertex, dist, off, pred, rel)."""
+        nv, ne, _ = self.sssp_kept_dag_edges_build(target, max_distance)
+        return self._dag_whole(self.sssp_kept_dag_read, self.sssp_kept_dag_read_relations,
+                               load().jg_sssp_kept_dag_read, nv, ne, np.int64)
 
     def sssp_keep(self, source, direction=DIR_BOTH):
         """jg_sssp_keep: the smallest summed weights from `source` along `direction` (weights >= 1; DIR_BOTH
@@ -855,6 +901,20 @@ class Graph:
         nv, ne, _ = self.sssp_kept_dag_edges_f64_build(target, max_distance)
         return self._dag_whole(self.sssp_kept_dag_f64_read, self.sssp_kept_dag_read_edges,
                                load().jg_sssp_kept_dag_read_f64, nv, ne)
+
+    def sssp_kept_dag_relations_f64(self, target=None, max_distance=-1.0):
+        """sssp_kept_dag_edges_f64 with relation ids in place of ordinals: (vertex, dist, off, pred, rel)."""
+        nv, ne, _ = self.sssp_kept_dag_edges_f64_build(target, max_distance)
+        return self._dag_whole(self.sssp_kept_dag_f64_read, self.sssp_kept_dag_read_relations,
+                               load().jg_sssp_kept_dag_read_f64, nv, ne, np.int64)
+
+    def edge_relations(self, ordinals):
+        """jg_graph_edge_relations: the JanusGraph relation id (int64) of each edge ordinal, gathered on the device
+        (a graph of a Builder.keep_relations builder finished with ADJ_EDGE_INDEX)."""
+        o = np.ascontiguousarray(np.atleast_1d(ordinals), np.uint32)
+        rel = np.empty(max(len(o), 1), np.int64)
+        check(load().jg_graph_edge_relations(self._h, _ptr(o), len(o), _ptr(rel)))
+        return rel[:len(o)]
 
     def neighbors(self, rows, direction=DIR_BOTH):
         """jg_graph_neighbors: (off, nbr) CSR of the given output-order rows, in output-order indices."""

@@ -644,6 +644,8 @@ struct jg_builder {
     int64_t wkey = -1;
     std::vector<int64_t> wkey_ids;
     std::vector<int8_t> wkey_types;
+    bool weight_key_f64 = false;  // jg_builder_set_weight_key_f64 (wkey, wkey_ids, wkey_types as above)
+    bool keep_relations = false;  // jg_builder_keep_relations: rows only, a relation id beside every edge (dec->rel)
     bool keep_labels = false;  // jg_builder_keep_labels: a label beside every edge (ids: lab; rows: dec->lab)
     bool sealed = false;       // after the first jg_builder_finish_labels: no more chunks
     jg::DevBuf<int64_t> lab;
@@ -1066,6 +1068,7 @@ int jg_builder_add_vertices(jg_builder* b, const int64_t* vid, int64_t n) {
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     if (b->sealed) jg::fail(JG_ERR_STATE, "builder sealed by jg_builder_finish_labels: no more chunks");
     if (b->mode == 2) jg::fail(JG_ERR_STATE, "builder holds edgestore rows: vertices come from the rows");
+    if (b->keep_relations) jg::fail(JG_ERR_ARG, "the builder keeps relation ids: it takes edgestore rows only");
     b->mode = 1;
     jg::DeviceGuard dg(builder_device(b));
     builder_append(b->vid, b->n, vid, n, builder_stream(b));
@@ -1081,6 +1084,7 @@ void builder_add_edges(jg_builder* b, const int64_t* src, const int64_t* dst, co
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     if (b->sealed) jg::fail(JG_ERR_STATE, "builder sealed by jg_builder_finish_labels: no more chunks");
     if (b->mode == 2) jg::fail(JG_ERR_STATE, "builder holds edgestore rows: edges come from the rows");
+    if (b->keep_relations) jg::fail(JG_ERR_ARG, "the builder keeps relation ids: it takes edgestore rows only");
     if (labeled && !b->keep_labels)
         jg::fail(JG_ERR_STATE, "jg_builder_add_labeled_edges needs jg_builder_keep_labels before the first chunk");
     if (!labeled && b->keep_labels)
@@ -1125,6 +1129,17 @@ int jg_builder_keep_labels(jg_builder* b) {
     JG_GUARD_END
 }
 
+int jg_builder_keep_relations(jg_builder* b) {
+    JG_GUARD_BEGIN
+    JG_ARG(b, "null builder");
+    if (b->finished || b->sealed || b->mode != 0)
+        jg::fail(JG_ERR_STATE, "jg_builder_keep_relations must precede every chunk");
+    if (b->query_limit > 0)
+        jg::fail(JG_ERR_STATE, "relation ids cannot be kept under a query limit: the capped lists are not the edge list");
+    b->keep_relations = true;
+    JG_GUARD_END
+}
+
 int jg_builder_set_schema(jg_builder* b, const int64_t* type_ids, const int8_t* type_mult, int32_t ntypes,
                           int32_t partition_bits) {
     JG_GUARD_BEGIN
@@ -1148,6 +1163,9 @@ int jg_builder_set_query_limit(jg_builder* b, int64_t limit, int32_t in_entries)
     if (limit > 0 && b->keep_labels)
         jg::fail(JG_ERR_STATE, "a query limit cannot be set on a label-keeping builder: typed scopes are fitted queries, "
                                "never capped");
+    if (limit > 0 && b->keep_relations)
+        jg::fail(JG_ERR_STATE, "a query limit cannot be set on a builder that keeps relation ids: the capped lists are "
+                               "not the edge list");
     b->query_limit = limit;
     b->in_entries = in_entries;
     JG_GUARD_END
@@ -1161,7 +1179,32 @@ int jg_builder_set_weight_key(jg_builder* b, int64_t weight_key, const int64_t* 
     for (int32_t i = 0; i < nkeys; ++i)
         JG_ARG(key_types[i] >= 0 && key_types[i] <= JG_PROP_STRING, "property type outside JG_PROP_*");
     if (b->finished || b->mode != 0) jg::fail(JG_ERR_STATE, "jg_builder_set_weight_key must precede every chunk");
+    if (b->weight_key_f64) jg::fail(JG_ERR_STATE, "the builder already decodes an f64 weight key");
     b->weight_key = true;
+    b->wkey = weight_key;
+    b->wkey_ids.assign(key_ids, key_ids + nkeys);
+    b->wkey_types.assign(key_types, key_types + nkeys);
+    JG_GUARD_END
+}
+
+int jg_builder_set_weight_key_f64(jg_builder* b, int64_t weight_key, const int64_t* key_ids, const int8_t* key_types,
+                                  int32_t nkeys) {
+    JG_GUARD_BEGIN
+    JG_ARG(b, "null builder");
+    JG_ARG(weight_key >= 0 && nkeys >= 0 && (nkeys == 0 || (key_ids && key_types)), "bad weight key arguments");
+    if (b->finished || b->mode != 0) jg::fail(JG_ERR_STATE, "jg_builder_set_weight_key_f64 must precede every chunk");
+    if (b->weight_key || b->weight_key_f64) jg::fail(JG_ERR_STATE, "the builder already decodes a weight key");
+    // the weight key's own type first: a Float key, a type outside JG_PROP_* or a key the table lacks is refused
+    // as unsupported, whatever else the table holds
+    int wtype = 0;
+    for (int32_t i = 0; i < nkeys; ++i)
+        if (key_ids[i] == weight_key) wtype = key_types[i];
+    if (wtype != JG_PROP_DOUBLE && wtype != JG_PROP_INT && wtype != JG_PROP_LONG)
+        jg::fail(JG_ERR_UNSUPPORTED, "jg_builder_set_weight_key_f64: the weight key must be a Double, Integer or Long key "
+                                     "of the table (Floats add in binary32)");
+    for (int32_t i = 0; i < nkeys; ++i)
+        JG_ARG(key_types[i] >= 0 && key_types[i] <= JG_PROP_STRING, "property type outside JG_PROP_*");
+    b->weight_key_f64 = true;
     b->wkey = weight_key;
     b->wkey_ids.assign(key_ids, key_ids + nkeys);
     b->wkey_types.assign(key_types, key_types + nkeys);
@@ -1182,8 +1225,11 @@ int jg_builder_add_rows(jg_builder* b, const uint64_t* row_keys, int64_t nrows, 
                                                         (int32_t)b->type_ids.size(), b->pbits, builder_device(b));
         b->dec->set_query_limit(b->query_limit);
         b->dec->set_keep_labels(b->keep_labels);
+        b->dec->set_keep_relations(b->keep_relations);
         if (b->weight_key)
             b->dec->set_weight_key(b->wkey, b->wkey_ids.data(), b->wkey_types.data(), (int32_t)b->wkey_ids.size());
+        if (b->weight_key_f64)
+            b->dec->set_weight_key_f64(b->wkey, b->wkey_ids.data(), b->wkey_types.data(), (int32_t)b->wkey_ids.size());
     }
     jg::EdgestoreRows r{row_keys, nrows,      row_entry_off, bytes,
                         nbytes,   entry_off,  value_pos,     nentries,
@@ -1201,7 +1247,14 @@ int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     *out = nullptr;
     jg::Ctx& c = *b->ctx;
-    edge_index_check(flags, c, b->mode == 2 ? "edgestore rows keep no relation ids to number their edges by" : nullptr);
+    // rows number their edges by the decoder's kept list once something is held beside it to read through the
+    // ordinals: the relation ids (jg_builder_keep_relations) or the doubles (jg_builder_set_weight_key_f64)
+    const bool rows_list = b->keep_relations || b->weight_key_f64;
+    edge_index_check(flags, c, b->mode == 2 && !rows_list ? "edgestore rows keep no relation ids to number their edges by"
+                                                          : nullptr);
+    if (b->weight_key_f64 && !(flags & JG_ADJ_EDGE_INDEX))
+        jg::fail(JG_ERR_ARG, "jg_builder_set_weight_key_f64 needs JG_ADJ_EDGE_INDEX at finish (the doubles are gathered "
+                             "through the ordinals)");
     auto gh = std::make_unique<jg_graph>(&c);
     jg::Graph& g = gh->impl;
     g.flags = flags;
@@ -1233,6 +1286,16 @@ int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out) {
         }
         jg::build_from_device_ids(g, dev0, builder_stream(b), d.vid.get(), d.n, d.src.get(), d.dst.get(),
                                   d.weighted == 1 ? d.w.get() : nullptr, d.m, d.query_limit() > 0 ? &cap : nullptr);
+        if (d.weight_f64()) {  // statistics, gate and gather as jg_graph_set_weights_f64 does them on the same values
+            if (d.wf.size() == 0) d.wf.alloc(1);
+            jg::graph_set_weights_f64_device(g, d.wf.get(), d.m, "jg_builder_finish (jg_builder_set_weight_key_f64)");
+        }
+        if (d.keep_relations() && (flags & JG_ADJ_EDGE_INDEX)) {  // without the flag the table is dropped
+            if (d.rel.size() == 0) d.rel.alloc(1);
+            g.edge_rel.swap(d.rel);
+            g.has_edge_rel = true;
+            g.info.device_bytes += 8 * d.m;
+        }
     } else {
         jg::DeviceGuard dg(dev0);
         if (b->vid.size() == 0) b->vid.alloc(1);
@@ -1622,6 +1685,13 @@ int jg_bfs_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint32
     JG_GUARD_END
 }
 
+int jg_bfs_kept_dag_read_relations(jg_graph* g, int64_t first, int64_t count, int64_t* rel_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::bfs_kept_dag_read_relations(g->impl, first, count, rel_out);
+    JG_GUARD_END
+}
+
 int jg_sssp_keep(jg_graph* g, int64_t source_vid, int32_t direction) {
     JG_GUARD_BEGIN
     JG_ARG(g, "null graph");
@@ -1671,6 +1741,20 @@ int jg_sssp_kept_dag_read_edges(jg_graph* g, int64_t first, int64_t count, uint3
     JG_GUARD_BEGIN
     JG_ARG(g, "null graph");
     jg::sssp_kept_dag_read_edges(g->impl, first, count, edge_out);
+    JG_GUARD_END
+}
+
+int jg_sssp_kept_dag_read_relations(jg_graph* g, int64_t first, int64_t count, int64_t* rel_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::sssp_kept_dag_read_relations(g->impl, first, count, rel_out);
+    JG_GUARD_END
+}
+
+int jg_graph_edge_relations(const jg_graph* g, const uint32_t* ordinals, int64_t count, int64_t* rel_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    jg::graph_edge_relations(g->impl, ordinals, count, rel_out);
     JG_GUARD_END
 }
 

@@ -147,7 +147,8 @@ __device__ __forceinline__ Decoded decode_entry(const EntryView& a, const uint8_
 // BooleanSerializer 1, DateSerializer 8, FloatSerializer 4, DoubleSerializer 8, UUIDSerializer 16;
 // IntegerSerializer a signed VariableLong; StringSerializer (no flag byte) its own length header.
 // Error bits of the snapshot (any set bit fails the build before the CSR is cut)
-enum : int32_t { kErrBadKey = 1, kErrPartitioned = 2, kErrMalformed = 4, kErrWeightType = 8, kErrWeightValue = 16 };
+enum : int32_t { kErrBadKey = 1, kErrPartitioned = 2, kErrMalformed = 4, kErrWeightType = 8, kErrWeightValue = 16,
+               kErrWeightRange = 32 };
 
 // VariableLong.read: the zig-zag-free sign encoding |v| << 1 | sign (VariableLong.java:133-152)
 __device__ __forceinline__ int64_t read_signed(const uint8_t* __restrict__ b, int64_t& pos, int64_t len, bool& bad) {
@@ -183,10 +184,12 @@ __device__ __forceinline__ void skip_string(const uint8_t* __restrict__ b, int64
     if (pos > len) bad = true;
 }
 
-// The weight of one entry: JG_WEIGHT_ABSENT when the edge has no (non-null Integer) weight; *err gets
-// kErrWeightType when a property of an unknown type precedes the weight key (its length is unknown).
-__device__ __forceinline__ int32_t decode_weight(const uint8_t* __restrict__ b, int64_t pos, int64_t len,
-                                                 const WeightSchema& w, int32_t* err) {
+// The walk over an edge's inline properties up to the weight key: true with pos at the first byte of the key's
+// non-null value (past its flag byte); false when the edge has no such value (no key, a null).  *err gets
+// kErrWeightType when a property of an unknown type precedes the weight key (its length is unknown) and
+// kErrMalformed when the bytes do not parse.
+__device__ __forceinline__ bool seek_weight(const uint8_t* __restrict__ b, int64_t& pos, int64_t len,
+                                            const WeightSchema& w, int32_t* err) {
     bool bad = false;
     while (pos < len) {
         const int64_t kid = read_unsigned(b, pos, len, bad);
@@ -203,45 +206,96 @@ __device__ __forceinline__ int32_t decode_weight(const uint8_t* __restrict__ b, 
         }
         if (type <= 0 || type > JG_PROP_UUID) {
             atomicOr(err, kErrWeightType);
-            return JG_WEIGHT_ABSENT;
+            return false;
         }
         if (pos >= len) { bad = true; break; }
         const uint8_t flag = b[pos++];
         if (flag == 0xFF) {  // a null value
-            if (kid == w.key) return JG_WEIGHT_ABSENT;
+            if (kid == w.key) return false;
             continue;
         }
         if (flag != 0) { bad = true; break; }
+        if (kid == w.key) return true;
         if (type == JG_PROP_INT) {
-            const int64_t v = read_signed(b, pos, len, bad);
-            if (kid == w.key) {
-                if (bad || v < INT32_MIN || v > INT32_MAX) break;
-                if (v == INT32_MIN) {  // the absent marker itself: refuse rather than drop the weight
-                    atomicOr(err, kErrWeightValue);
-                    return JG_WEIGHT_ABSENT;
-                }
-                return (int32_t)v;
-            }
+            (void)read_signed(b, pos, len, bad);
             continue;
         }
-        if (kid == w.key) return JG_WEIGHT_ABSENT;  // not an Integer: Fulgora's <Integer> cast throws
         constexpr int8_t kWidth[JG_PROP_UUID + 1] = {0, 1, 2, 0, 8, 2, 1, 8, 4, 8, 16};  // by JG_PROP_*
         pos += kWidth[type];
     }
     if (bad || pos > len) atomicOr(err, kErrMalformed);
-    return JG_WEIGHT_ABSENT;
+    return false;
+}
+
+// The Integer weight of one entry (the schema's key is an Integer key, set_weight_key): JG_WEIGHT_ABSENT when the
+// edge has no non-null value for it or the value is no int32.
+__device__ __forceinline__ int32_t decode_weight(const uint8_t* __restrict__ b, int64_t pos, int64_t len,
+                                                 const WeightSchema& w, int32_t* err) {
+    if (!seek_weight(b, pos, len, w, err)) return JG_WEIGHT_ABSENT;
+    bool bad = false;
+    const int64_t v = read_signed(b, pos, len, bad);
+    if (bad) {
+        atomicOr(err, kErrMalformed);
+        return JG_WEIGHT_ABSENT;
+    }
+    if (v < INT32_MIN || v > INT32_MAX) return JG_WEIGHT_ABSENT;
+    if (v == INT32_MIN) {  // the absent marker itself: refuse rather than drop the weight
+        atomicOr(err, kErrWeightValue);
+        return JG_WEIGHT_ABSENT;
+    }
+    return (int32_t)v;
+}
+
+// The weight of one entry as a double (set_weight_key_f64): NaN when the edge has no non-null value for the key
+// (the finish refuses such a list).  JG_PROP_DOUBLE: DoubleSerializer's 8 big-endian bytes of the IEEE bits;
+// JG_PROP_LONG: LongSerializer's 8 big-endian bytes of value - Long.MIN_VALUE (the sign bit flipped);
+// JG_PROP_INT: a signed VariableLong.  Integers convert exactly or not at all: |v| > 2^53 sets kErrWeightRange.
+// The value sits at any byte offset, so it is assembled from single-byte reads, none past the entry's end.
+__device__ __forceinline__ double decode_weight_f64(const uint8_t* __restrict__ b, int64_t pos, int64_t len,
+                                                    const WeightSchema& w, int32_t* err) {
+    const double absent = __builtin_nan("");
+    if (!seek_weight(b, pos, len, w, err)) return absent;
+    int64_t v;
+    if (w.key_type == JG_PROP_INT) {
+        bool bad = false;
+        v = read_signed(b, pos, len, bad);
+        if (bad) {
+            atomicOr(err, kErrMalformed);
+            return absent;
+        }
+    } else {
+        if (len - pos < 8) {  // the value is cut short
+            atomicOr(err, kErrMalformed);
+            return absent;
+        }
+        uint64_t u = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) u = (u << 8) | b[pos + i];
+        if (w.key_type == JG_PROP_DOUBLE) return __longlong_as_double((long long)u);
+        v = (int64_t)(u ^ 0x8000000000000000ull);
+    }
+    constexpr int64_t kExact = (int64_t)1 << 53;
+    if (v > kExact || v < -kExact) {
+        atomicOr(err, kErrWeightRange);
+        return absent;
+    }
+    return (double)v;
 }
 
 // One thread per entry: the weight of every OUT user edge (the kept entries' weights are compacted
-// with the edges, as host-given weights are).
+// with the edges, as host-given weights are).  T = int32_t: the Integer route; double: the f64 route.
+template <typename T>
 __global__ __launch_bounds__(kBlock) void edgestore_weight_kernel(EntryView a, int64_t nentries, WeightSchema w,
-                                                                  int32_t* __restrict__ weight,
-                                                                  int32_t* __restrict__ err) {
+                                                                  T* __restrict__ weight, int32_t* __restrict__ err) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nentries; e += (int64_t)gridDim.x * blockDim.x) {
         const uint8_t* b = a.bytes + a.off[e];
         const int64_t len = a.off[e + 1] - a.off[e];
         const Decoded d = decode_entry(a, b, len, a.vpos[e]);
-        weight[e] = d.dir == 0 && d.visible ? decode_weight(b, d.vstart, len, w, err) : JG_WEIGHT_ABSENT;
+        const bool edge = d.dir == 0 && d.visible;
+        if constexpr (sizeof(T) == sizeof(double))
+            weight[e] = edge ? decode_weight_f64(b, d.vstart, len, w, err) : __builtin_nan("");
+        else
+            weight[e] = edge ? decode_weight(b, d.vstart, len, w, err) : JG_WEIGHT_ABSENT;
     }
 }
 
@@ -395,6 +449,10 @@ __global__ void block_rows_kernel(const int64_t* __restrict__ row_off, int64_t n
     }
 }
 
+// kRel (jg_builder_keep_relations): the relation id of every taken OUT entry goes to rel[e].  A template
+// parameter, not a null test as for etype: with the store compiled in, the ids' decode keeps the relation id live
+// and the kernel of a builder that asked for nothing measured 2-3 % slower (RMAT-20, 1.00 -> 1.02 ms).
+template <bool kRel>
 __global__ __launch_bounds__(kBlock) void edgestore_edges_kernel(EntryView a, const int64_t* __restrict__ row_off,
                                                                   const int64_t* __restrict__ block_row,
                                                                   int64_t nrows, int64_t nent,
@@ -403,6 +461,7 @@ __global__ __launch_bounds__(kBlock) void edgestore_edges_kernel(EntryView a, co
                                                                   bool with_in, uint8_t* __restrict__ take,
                                                                   int64_t* __restrict__ src, int64_t* __restrict__ dst,
                                                                   int64_t* __restrict__ etype,
+                                                                  int64_t* __restrict__ rel,
                                                                   int32_t* __restrict__ err) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kStageWords];
     __shared__ int64_t win_off[kRowWin + 1];
@@ -469,6 +528,7 @@ __global__ __launch_bounds__(kBlock) void edgestore_edges_kernel(EntryView a, co
                     src[e] = row_vid[r];
                     dst[e] = other;
                     if (etype) etype[e] = d.type_id;  // jg_builder_keep_labels (null otherwise: a uniform branch)
+                    if constexpr (kRel) rel[e] = d.rel;
                 } else if (with_in && d.dir == 1 && d.visible) {  // the IN entry of edge other -> row
                     t = 2;
                     src[e] = other;
@@ -693,7 +753,7 @@ struct EdgestoreChunk {
     int64_t R = 0, E = 0, nbytes = 0;
     PinnedBuf staging;
     DevBuf<uint8_t> d_bytes, keep, keep_v, take, out_flag, in_flag;
-    DevBuf<int64_t> d_off, d_roff, row_vid, esrc, edst, etype, block_row, pre;
+    DevBuf<int64_t> d_off, d_roff, row_vid, esrc, edst, etype, erel, block_row, pre;
     DevBuf<uint32_t> slice;
     DevBuf<unsigned long long> truncated;
     DevBuf<uint8_t> d_meta8;   // narrow staging: entry lengths then value positions
@@ -702,6 +762,7 @@ struct EdgestoreChunk {
     hipEvent_t tc = nullptr;   // after the chunk's copies
     DevBuf<uint64_t> d_keys;
     DevBuf<int32_t> d_vpos, err, d_w;
+    DevBuf<double> d_wf;  // set_weight_key_f64: one double per entry
     bool weighted = false;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool pending = false;
@@ -800,8 +861,9 @@ EdgestoreDecoder::EdgestoreDecoder(const int64_t* type_ids, const int8_t* type_m
     types_ = std::make_unique<TypeTable>(type_ids, type_mult, ntypes, streams_[0]);
 }
 
-void EdgestoreDecoder::set_weight_key(int64_t key, const int64_t* ids, const int8_t* types, int32_t n) {
+void EdgestoreDecoder::set_weight_schema(int64_t key, const int64_t* ids, const int8_t* types, int32_t n) {
     if (chunks_added_) fail(JG_ERR_STATE, "the weight key must be set before the first chunk");
+    if (weight_key_set_ || weight_f64_) fail(JG_ERR_STATE, "a weight key is already set");
     if (key < 0 || n < 0 || (n && (!ids || !types))) fail(JG_ERR_ARG, "bad weight key arguments");
     std::vector<std::pair<int64_t, int8_t>> t((size_t)n);
     for (int32_t i = 0; i < n; ++i) t[i] = {ids[i], types[i]};
@@ -816,14 +878,23 @@ void EdgestoreDecoder::set_weight_key(int64_t key, const int64_t* ids, const int
         hty[i] = t[i].second;
         if (t[i].first == key) wschema_.key_type = t[i].second;
     }
-    if (wschema_.key_type != JG_PROP_INT) wschema_.key = -1;  // no Integer weight on any edge: all absent
     wschema_.n = n;
     DeviceGuard dg(device_);
     wkeys_.alloc(std::max(n, 1));
     wtypes_.alloc(std::max(n, 1));
     copy_h2d(wkeys_.get(), hid.data(), hid.size() * sizeof(int64_t), streams_[0]);
     copy_h2d(wtypes_.get(), hty.data(), hty.size() * sizeof(int8_t), streams_[0]);
+}
+
+void EdgestoreDecoder::set_weight_key(int64_t key, const int64_t* ids, const int8_t* types, int32_t n) {
+    set_weight_schema(key, ids, types, n);
+    if (wschema_.key_type != JG_PROP_INT) wschema_.key = -1;  // no Integer weight on any edge: all absent
     weight_key_set_ = true;
+}
+
+void EdgestoreDecoder::set_weight_key_f64(int64_t key, const int64_t* ids, const int8_t* types, int32_t n) {
+    set_weight_schema(key, ids, types, n);
+    weight_f64_ = true;
 }
 
 EdgestoreDecoder::~EdgestoreDecoder() {
@@ -855,7 +926,8 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
     const auto h0 = HostClock::now();
     check_rows(r);
     const bool dev_w = weight_key_set_;  // weights decoded here from the rows (set_weight_key; key -1: all absent)
-    if (dev_w && r.weight) fail(JG_ERR_ARG, "entry weights given while the weight key decodes them on the GPU");
+    if ((dev_w || weight_f64_) && r.weight)
+        fail(JG_ERR_ARG, "entry weights given while the weight key decodes them on the GPU");
     const int wmode = (r.weight || dev_w) ? 1 : 0;
     if (weighted >= 0 && weighted != wmode) fail(JG_ERR_ARG, "entry weights must be given for every chunk or none");
     weighted = wmode;
@@ -950,6 +1022,8 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
     fit(c.esrc, E);
     fit(c.edst, E);
     if (keep_labels_) fit(c.etype, E);
+    if (keep_relations_) fit(c.erel, E);
+    if (weight_f64_) fit(c.d_wf, E);
     fit(c.block_row, (E + kChunk - 1) / kChunk + 1);
     fit(c.d_keys, R);
     fit(c.d_vpos, E);
@@ -994,7 +1068,14 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
         WeightSchema w = wschema_;
         w.ids = wkeys_.get();
         w.types = wtypes_.get();
-        edgestore_weight_kernel<<<grid_for(E), kBlock, 0, s>>>(a, E, w, c.d_w.get(), c.err.get());
+        edgestore_weight_kernel<int32_t><<<grid_for(E), kBlock, 0, s>>>(a, E, w, c.d_w.get(), c.err.get());
+        JG_LAUNCH_CHECK();
+    }
+    if (weight_f64_ && E) {
+        WeightSchema w = wschema_;
+        w.ids = wkeys_.get();
+        w.types = wtypes_.get();
+        edgestore_weight_kernel<double><<<grid_for(E), kBlock, 0, s>>>(a, E, w, c.d_wf.get(), c.err.get());
         JG_LAUNCH_CHECK();
     }
     if (R) {
@@ -1005,9 +1086,11 @@ void EdgestoreDecoder::add(const EdgestoreRows& r) {
     if (E) {
         block_rows_kernel<<<grid_for(R), kBlock, 0, s>>>(c.d_roff.get(), R, c.block_row.get());
         JG_LAUNCH_CHECK();
-        edgestore_edges_kernel<<<grid_for((E + kEpt - 1) / kEpt, kBlock, 256 * 16), kBlock, 0, s>>>(
+        const auto edges_kernel = keep_relations_ ? edgestore_edges_kernel<true> : edgestore_edges_kernel<false>;
+        edges_kernel<<<grid_for((E + kEpt - 1) / kEpt, kBlock, 256 * 16), kBlock, 0, s>>>(
             a, c.d_roff.get(), c.block_row.get(), R, E, c.keep.get(), c.row_vid.get(), pbits_, capped, c.take.get(),
-            c.esrc.get(), c.edst.get(), keep_labels_ ? c.etype.get() : nullptr, c.err.get());
+            c.esrc.get(), c.edst.get(), keep_labels_ ? c.etype.get() : nullptr,
+            keep_relations_ ? c.erel.get() : nullptr, c.err.get());
         JG_LAUNCH_CHECK();
     }
     if (capped) {
@@ -1058,10 +1141,13 @@ void EdgestoreDecoder::complete(int slot) {
         fail(JG_ERR_UNSUPPORTED, "an edge carries a property of unknown type before the weight key");
     if (herr & kErrWeightValue)
         fail(JG_ERR_UNSUPPORTED, "an edge weight equals Integer.MIN_VALUE (the absent-weight marker)");
+    if (herr & kErrWeightRange)
+        fail(JG_ERR_UNSUPPORTED, "an integer edge weight beyond 2^53 has no exact double");
     const int64_t cap = std::max<int64_t>(std::max(c.R, c.E), 1);
     if ((int64_t)idx_.size() < cap) idx_.alloc(cap);
     if ((int64_t)tmp_.size() < cap) tmp_.alloc(cap);
     if (c.weighted && (int64_t)tmpw_.size() < cap) tmpw_.alloc(cap);
+    if (weight_f64_ && (int64_t)tmpd_.size() < cap) tmpd_.alloc(cap);
     const int64_t nk = prim::compact_indices(c.keep_v.get(), c.R, idx_.get(), cpos_, cscan_, s);
     if (nk) {
         gather_kernel<int64_t><<<grid_for(nk), kBlock, 0, s>>>(c.row_vid.get(), idx_.get(), nk, tmp_.get());
@@ -1112,6 +1198,16 @@ void EdgestoreDecoder::complete(int slot) {
             gather_kernel<int64_t><<<grid_for(mk), kBlock, 0, s>>>(c.etype.get(), idx_.get(), mk, tmp_.get());
             JG_LAUNCH_CHECK();
             grow_append(lab, ml, tmp_.get(), mk, s);
+        }
+        if (keep_relations_) {  // their relation ids likewise
+            gather_kernel<int64_t><<<grid_for(mk), kBlock, 0, s>>>(c.erel.get(), idx_.get(), mk, tmp_.get());
+            JG_LAUNCH_CHECK();
+            grow_append(rel, mr, tmp_.get(), mk, s);
+        }
+        if (weight_f64_) {  // and their doubles
+            gather_kernel<double><<<grid_for(mk), kBlock, 0, s>>>(c.d_wf.get(), idx_.get(), mk, tmpd_.get());
+            JG_LAUNCH_CHECK();
+            grow_append(wf, mwf, tmpd_.get(), mk, s);
         }
     }
     JG_HIP(hipStreamSynchronize(s));

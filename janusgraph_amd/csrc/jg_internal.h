@@ -339,6 +339,10 @@ struct Graph {
     bool wdag_f64 = false;            // the held weighted DAG (Shard::wdag) was built from such a plane
     // JG_ADJ_EDGE_INDEX: the length of the caller's edge list (what Csr::eidx indexes); -1 without the flag
     int64_t edge_list_m = -1;
+    // jg_builder_keep_relations + JG_ADJ_EDGE_INDEX (rows): the JanusGraph relation id of every listed edge,
+    // edge_rel[ordinal] for ordinals [0, edge_list_m), on the first shard's device (counted in info.device_bytes)
+    bool has_edge_rel = false;
+    DevBuf<int64_t> edge_rel;
     // jg_graph_set_weights_f64: the double weights are set (Csr::wf beside every built adjacency), and their
     // smallest, largest and mean value (a fixed-order reduction: the same bits on every run)
     bool has_wf = false;
@@ -510,7 +514,8 @@ struct EdgestoreChunk;
 // The property keys an edge value may hold before the weight key (jg_builder_set_weight_key)
 struct WeightSchema {
     int64_t key = -1;              // inline id of the weight key (-1: none)
-    int8_t key_type = 0;           // its JG_PROP_* type (weights are read only for JG_PROP_INT)
+    int8_t key_type = 0;           // its JG_PROP_* type (Integer route: read only for JG_PROP_INT; f64 route:
+                                   // JG_PROP_DOUBLE, JG_PROP_INT or JG_PROP_LONG)
     const int64_t* ids = nullptr;  // sorted inline ids of the property keys (device)
     const int8_t* types = nullptr;
     int32_t n = 0;
@@ -532,6 +537,18 @@ struct EdgestoreDecoder {
     void set_query_limit(int64_t limit) { limit_ = limit; }
     // jg_builder_set_weight_key: decode every OUT edge's Integer weight from its value on the GPU
     void set_weight_key(int64_t key, const int64_t* ids, const int8_t* types, int32_t n);
+    // jg_builder_set_weight_key_f64: every OUT edge's weight as a double (wf[0, m), NaN where the edge has no
+    // non-null value); the key's type is JG_PROP_DOUBLE, JG_PROP_INT or JG_PROP_LONG (the caller checked)
+    void set_weight_key_f64(int64_t key, const int64_t* ids, const int8_t* types, int32_t n);
+    bool weight_f64() const { return weight_f64_; }
+    DevBuf<double> wf;
+    int64_t mwf = 0;
+    // jg_builder_keep_relations (before the first add): rel[0, m) = the relation id of each kept edge, aligned
+    // with src / dst
+    void set_keep_relations(bool on) { keep_relations_ = on; }
+    bool keep_relations() const { return keep_relations_; }
+    DevBuf<int64_t> rel;
+    int64_t mr = 0;
     int64_t query_limit() const { return limit_; }
     // jg_builder_keep_labels (before the first add): lab[0, m) = the relation type id of each kept edge,
     // aligned with src / dst
@@ -551,13 +568,15 @@ struct EdgestoreDecoder {
     void complete(int slot);
     int pbits_, device_;
     int64_t limit_ = 0;
-    bool keep_labels_ = false;
+    bool keep_labels_ = false, keep_relations_ = false, weight_f64_ = false;
+    void set_weight_schema(int64_t key, const int64_t* ids, const int8_t* types, int32_t n);
     int next_ = 0;
     hipStream_t streams_[2] = {nullptr, nullptr};
     std::unique_ptr<EdgestoreChunk> chunks_[2];
     std::unique_ptr<TypeTable> types_;
     DevBuf<int64_t> idx_, tmp_, cpos_, cscan_;
     DevBuf<int32_t> tmpw_;
+    DevBuf<double> tmpd_;
     WeightSchema wschema_;         // key < 0: no device weight decode
     bool weight_key_set_ = false;  // set_weight_key was called (even if no Integer key exists)
     DevBuf<int64_t> wkeys_;
@@ -608,6 +627,8 @@ void bfs_kept_dag(Graph& g, int s, const uint8_t* target, int64_t* nv_out, int64
 void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
                        int64_t* off_out, int32_t* pred_out);
 void bfs_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out);
+// the relation ids of the same entries (Graph::edge_rel gathered through the ordinals on the device)
+void bfs_kept_dag_read_relations(Graph& g, int64_t first, int64_t count, int64_t* rel_out);
 void bfs_kept_dag_drop(Graph& g);
 // Zeroes the occupied positions of a shard's gathered vector of adjacency `adj` (own rows + peer runs).
 void zero_gathered(const Graph& g, const Shard& sh, uint32_t adj, void* v, size_t eb);
@@ -617,6 +638,10 @@ void graph_neighbors(const Graph& g, int direction, const int64_t* rows, int64_t
 // jg_graph_neighbor_edges: the edge ordinals of the same entries (JG_ADJ_EDGE_INDEX graphs: one shard)
 void graph_neighbor_edges(const Graph& g, int direction, const int64_t* rows, int64_t nrows, int64_t* off_out,
                           uint32_t* edge_out);
+// jg_graph_edge_relations: rel_out[i] = the relation id of edge ordinal ordinals[i] (Graph::edge_rel)
+void graph_edge_relations(const Graph& g, const uint32_t* ordinals, int64_t count, int64_t* rel_out);
+// the same for count ordinals already on shard 0's device (the edge-listing DAGs' entries), on its stream
+void gather_edge_relations(const Graph& g, const uint32_t* d_ordinals, int64_t count, int64_t* rel_out);
 void shortest_distance_run(Graph& g, int64_t seed_vid, int max_depth, int64_t* dist_out);
 // jg_sssp_keep / jg_sssp_kept_row / jg_sssp_kept_release (jg_sssp.hip): one shard; the plane stays in
 // Shard::sssp_dist
@@ -630,10 +655,14 @@ void sssp_kept_dag(Graph& g, const uint8_t* target, int64_t max_distance, int64_
 void sssp_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int64_t* dist_out,
                         int64_t* off_out, int32_t* pred_out);
 void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out);
+void sssp_kept_dag_read_relations(Graph& g, int64_t first, int64_t count, int64_t* rel_out);
 void sssp_kept_dag_drop(Graph& g);
 // jg_graph_set_weights_f64, jg_sssp_keep_f64, jg_sssp_kept_row_f64 (jg_sssp.hip) and the f64 flavours of the
 // weighted DAG (jg_pathdag.hip): distances travel as the bit patterns of doubles
 void graph_set_weights_f64(Graph& g, const double* weight, int64_t m);
+// its device half: dw[0, m) already on the shard's device (the statistics check, the gate, the gather per
+// adjacency); `who` names the caller in the error texts (a rows builder's finish hands it the decoded doubles)
+void graph_set_weights_f64_device(Graph& g, const double* dw, int64_t m, const char* who);
 void sssp_keep_f64(Graph& g, int64_t source_vid, int direction);
 void sssp_kept_row_f64(Graph& g, double* dist_out);
 void sssp_kept_dag_f64(Graph& g, const uint8_t* target, double max_distance, int64_t* nv_out, int64_t* ne_out,

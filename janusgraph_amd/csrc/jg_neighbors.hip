@@ -173,4 +173,46 @@ void graph_neighbor_edges(const Graph& g, int direction, const int64_t* rows, in
     copy_d2h(edge_out, dout.get(), (size_t)off_out[nrows] * sizeof(uint32_t), sh.stream);
 }
 
+namespace {
+// out[i] = rel[ord[i]]; an ordinal outside the list [0, m) writes nothing and raises *bad
+__global__ void rel_gather_kernel(const int64_t* __restrict__ rel, int64_t m, const uint32_t* __restrict__ ord,
+                                  int64_t n, int64_t* __restrict__ out, int32_t* __restrict__ bad) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = ord[i];
+        if (o < m) out[i] = rel[o];
+        else atomicOr(bad, 1);
+    }
+}
+}  // namespace
+
+// One gather into a staging buffer and one copy out: only the relation ids cross, never the table.
+void gather_edge_relations(const Graph& g, const uint32_t* d_ordinals, int64_t count, int64_t* rel_out) {
+    if (!g.has_edge_rel)
+        fail(JG_ERR_UNSUPPORTED, "the graph holds no relation ids (a rows builder with jg_builder_keep_relations, "
+                                 "finished with JG_ADJ_EDGE_INDEX)");
+    if (count == 0) return;
+    const Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    DevBuf<int64_t> stage((size_t)count);
+    DevBuf<int32_t> bad(1);
+    JG_HIP(hipMemsetAsync(bad.get(), 0, sizeof(int32_t), sh.stream));
+    rel_gather_kernel<<<grid_for(count), kBlock, 0, sh.stream>>>(g.edge_rel.get(), g.edge_list_m, d_ordinals, count,
+                                                                stage.get(), bad.get());
+    JG_LAUNCH_CHECK();
+    int32_t hbad = 0;
+    copy_d2h(&hbad, bad.get(), sizeof(int32_t), sh.stream);
+    if (hbad) fail(JG_ERR_ARG, "edge ordinal outside the graph's edge list");
+    copy_d2h(rel_out, stage.get(), (size_t)count * sizeof(int64_t), sh.stream);
+}
+
+void graph_edge_relations(const Graph& g, const uint32_t* ordinals, int64_t count, int64_t* rel_out) {
+    if (count < 0 || (count > 0 && (!ordinals || !rel_out))) fail(JG_ERR_ARG, "bad arguments");
+    if (!g.has_edge_rel || count == 0) return gather_edge_relations(g, nullptr, 0, rel_out);
+    const Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    DevBuf<uint32_t> dord((size_t)count);
+    copy_h2d(dord.get(), ordinals, (size_t)count * sizeof(uint32_t), sh.stream);
+    gather_edge_relations(g, dord.get(), count, rel_out);
+}
+
 }  // namespace jg

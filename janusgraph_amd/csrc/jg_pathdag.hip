@@ -795,6 +795,24 @@ static void dag_read_edges(const Graph& g, const HeldDag<V>& h, const std::strin
     DeviceGuard dg(sh);
     dag_read_entries(sh, h.off, h.edge, first, count, edge_out);
 }
+// The same entries as relation ids: Graph::edge_rel gathered through the held ordinals on the device, so only the
+// ids cross to the host (parallel to pred_out, as the ordinals are)
+template <class V>
+static void dag_read_relations(const Graph& g, const HeldDag<V>& h, const std::string& name, const std::string& built_by,
+                               int64_t first, int64_t count, int64_t* rel_out) {
+    if (!g.has_edge_rel)
+        fail(JG_ERR_UNSUPPORTED, name + ": the graph holds no relation ids (jg_builder_keep_relations)");
+    if (h.nv < 0 || !h.edges) fail(JG_ERR_STATE, "no edge-listing " + built_by);
+    if (first < 0 || count < 0 || first > h.nv || count > h.nv - first)
+        fail(JG_ERR_ARG, "range outside the DAG's vertices");
+    if (h.nv == 0 || count == 0 || !rel_out) return;
+    const Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    int64_t b = 0, e = 0;
+    copy_d2h(&b, h.off.get() + first, sizeof(int64_t), sh.stream);
+    copy_d2h(&e, h.off.get() + first + count, sizeof(int64_t), sh.stream);
+    gather_edge_relations(g, h.edge.get() + b, e - b, rel_out);
+}
 
 void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_out, int32_t* depth_out,
                        int64_t* off_out, int32_t* pred_out) {
@@ -806,6 +824,11 @@ void bfs_kept_dag_read(Graph& g, int64_t first, int64_t count, int32_t* vertex_o
 void bfs_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {
     dag_read_edges(g, g.shards[0]->dag, "jg_bfs_kept_dag_read_edges", "predecessor DAG is held (jg_bfs_kept_dag_edges)",
                    first, count, edge_out);
+}
+
+void bfs_kept_dag_read_relations(Graph& g, int64_t first, int64_t count, int64_t* rel_out) {
+    dag_read_relations(g, g.shards[0]->dag, "jg_bfs_kept_dag_read_relations",
+                       "predecessor DAG is held (jg_bfs_kept_dag_edges)", first, count, rel_out);
 }
 
 void sssp_kept_dag_drop(Graph& g) {
@@ -957,6 +980,11 @@ void sssp_kept_dag_read_f64(Graph& g, int64_t first, int64_t count, int32_t* ver
 void sssp_kept_dag_read_edges(Graph& g, int64_t first, int64_t count, uint32_t* edge_out) {
     dag_read_edges(g, g.shards[0]->wdag, "jg_sssp_kept_dag_read_edges",
                    "weighted predecessor DAG is held (jg_sssp_kept_dag_edges)", first, count, edge_out);
+}
+
+void sssp_kept_dag_read_relations(Graph& g, int64_t first, int64_t count, int64_t* rel_out) {
+    dag_read_relations(g, g.shards[0]->wdag, "jg_sssp_kept_dag_read_relations",
+                       "weighted predecessor DAG is held (jg_sssp_kept_dag_edges)", first, count, rel_out);
 }
 
 }  // namespace jg

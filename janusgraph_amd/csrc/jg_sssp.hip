@@ -1207,20 +1207,31 @@ __global__ void wf_gather_kernel(const double* __restrict__ w, const uint32_t* _
 void graph_set_weights_f64(Graph& g, const double* weight, int64_t m) {
     if (!(g.flags & JG_ADJ_EDGE_INDEX) || g.edge_list_m < 0)
         fail(JG_ERR_UNSUPPORTED,
-             "jg_graph_set_weights_f64 needs a graph built from ids with JG_ADJ_EDGE_INDEX (its entries' edge ordinals)");
+             "jg_graph_set_weights_f64 needs a graph built with JG_ADJ_EDGE_INDEX (its entries' edge ordinals)");
     if (g.P != 1 || g.shards.size() != 1) fail(JG_ERR_UNSUPPORTED, "jg_graph_set_weights_f64: graphs of one shard only");
     if (m != g.edge_list_m) fail(JG_ERR_ARG, "jg_graph_set_weights_f64: m is not the length of the edge list the graph was built from");
     if (m > 0 && !weight) fail(JG_ERR_ARG, "weight is null");
     Shard& sh = *g.shards[0];
     DeviceGuard dg(sh);
-    hipStream_t s = sh.stream;
     DevBuf<double> dw((size_t)std::max<int64_t>(m, 1));
+    if (m > 0) copy_h2d(dw.get(), weight, (size_t)m * sizeof(double), sh.stream);
+    graph_set_weights_f64_device(g, dw.get(), m, "jg_graph_set_weights_f64");
+}
+
+// The device half: dw[0, m) = one double per listed edge on the shard's device (uploaded above, or decoded from
+// the rows by a builder with jg_builder_set_weight_key_f64, whose finish calls this).
+void graph_set_weights_f64_device(Graph& g, const double* dw, int64_t m, const char* who) {
+    const std::string name(who);
+    if (!(g.flags & JG_ADJ_EDGE_INDEX) || m != g.edge_list_m || g.P != 1 || g.shards.size() != 1)
+        fail(JG_ERR_STATE, name + ": the weights are not those of the graph's edge list");
+    Shard& sh = *g.shards[0];
+    DeviceGuard dg(sh);
+    hipStream_t s = sh.stream;
     double wmin = 0, wmax = 0, mean = 0;
     if (m > 0) {
-        copy_h2d(dw.get(), weight, (size_t)m * sizeof(double), s);
         const unsigned grid = grid_for(m, kBlock, kWfGrid);
         DevBuf<WfPart> part(grid);
-        wf_stats_kernel<<<grid, kBlock, 0, s>>>(dw.get(), m, part.get());
+        wf_stats_kernel<<<grid, kBlock, 0, s>>>(dw, m, part.get());
         JG_LAUNCH_CHECK();
         std::vector<WfPart> hp(grid);
         copy_d2h(hp.data(), part.get(), grid * sizeof(WfPart), s);
@@ -1231,15 +1242,15 @@ void graph_set_weights_f64(Graph& g, const double* weight, int64_t m) {
             r.sum += hp[k].sum;
             r.bad += hp[k].bad;
         }
-        if (r.bad) fail(JG_ERR_ARG, "jg_graph_set_weights_f64: every weight must be finite and > 0");
+        if (r.bad) fail(JG_ERR_ARG, name + ": every weight must be finite and > 0");
         wmin = r.mn;
         wmax = r.mx;
         mean = std::isfinite(r.sum) ? r.sum / (double)m : wmax;  // (a sum past DBL_MAX: any delta is correct)
         const double span = (double)std::max<int64_t>(g.n, 1) * wmax;
         if (!std::isfinite(span) || wmin < DBL_MIN || wmin < span * 0x1p-52)
             fail(JG_ERR_UNSUPPORTED,
-                 "jg_graph_set_weights_f64: the weights' range lets a relaxation be absorbed (needs wmin >= rows * wmax * 2^-52, "
-                 "wmin >= DBL_MIN, rows * wmax finite)");
+                 name + ": the weights' range lets a relaxation be absorbed (needs wmin >= rows * wmax * 2^-52, "
+                        "wmin >= DBL_MIN, rows * wmax finite)");
     }
     // gathered beside every built adjacency, into buffers of their own: a failure up to here left the graph as it was
     Csr* cs[3] = {&sh.out, &sh.in, &sh.both};
@@ -1247,10 +1258,10 @@ void graph_set_weights_f64(Graph& g, const double* weight, int64_t m) {
     for (int k = 0; k < 3; ++k) {
         const Csr& c = *cs[k];
         if (!c.present()) continue;
-        if (c.eidx.size() < (size_t)c.nnz) fail(JG_ERR_STATE, "jg_graph_set_weights_f64: an adjacency holds no edge ordinals");
+        if (c.eidx.size() < (size_t)c.nnz) fail(JG_ERR_STATE, name + ": an adjacency holds no edge ordinals");
         nw[k].alloc((size_t)std::max<int64_t>(c.nnz, 1));
         if (c.nnz > 0) {
-            wf_gather_kernel<<<grid_for(c.nnz), kBlock, 0, s>>>(dw.get(), c.eidx.get(), c.nnz, nw[k].get());
+            wf_gather_kernel<<<grid_for(c.nnz), kBlock, 0, s>>>(dw, c.eidx.get(), c.nnz, nw[k].get());
             JG_LAUNCH_CHECK();
         }
     }

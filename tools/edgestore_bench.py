@@ -11,7 +11,12 @@ edge OUT on its source row and IN on its target row.  Then times, on the GPU:
     the wall time of the add_rows calls (host staging + whatever the two chunk streams have not
     overlapped), the summed per-chunk copy and copy+decode event times, and finish;
 and checks every snapshot gives identical PageRank (the decoded one must equal the direct one).
-Prints one JSON line.  Usage: python tools/edgestore_bench.py [--scale 20] [--chunks 1,8,32]
+--relations: the chunked builder keeps relation ids (jg_builder_keep_relations) and finishes with
+ADJ_EDGE_INDEX; a sample of ordinals is read back (jg_graph_edge_relations) against the writer's ids.
+--f64-key: every edge carries a Double property (inline key id 9, a weight in [1, 2)), which the chunked
+builder decodes (jg_builder_set_weight_key_f64, finished with ADJ_EDGE_INDEX).  Each run then reports its
+build_ms beside the bytes its opt-ins add to the plain path's model.
+Prints one JSON line.  Usage: python tools/edgestore_bench.py [--scale 20] [--chunks 1,8,32] [--relations] [--f64-key]
 """
 import argparse
 import json
@@ -41,7 +46,10 @@ def backward_varint(v):
     return out, n
 
 
-def write_edgestore(scale, ef, seed):
+F64_KEY = 9  # inline id of the Double edge property of --f64-key
+
+
+def write_edgestore(scale, ef, seed, f64_key=False):
     from oracle import oracle as o  # input generator only: the RMAT edge list
     n = 1 << scale
     s, t = o.rmat_edges(scale, ef, seed)
@@ -58,6 +66,14 @@ def write_edgestore(scale, ef, seed):
     ob, on = backward_varint(other)
     rb, rn = backward_varint(relr)
     elen = 1 + on + rn
+    # --f64-key: the value holds one property: inline key id (one byte), flag 0, the big-endian IEEE bits
+    prop = None
+    if f64_key:
+        w = 1.0 + (relr % 1000) / 1000.0
+        prop = np.empty((2 * m, 10), np.uint8)
+        prop[:, 0] = 0x80 | F64_KEY
+        prop[:, 1] = 0
+        prop[:, 2:] = w.astype(">f8").view(np.uint8).reshape(-1, 8)
     # VertexExists entry per row: header 0x02 (SystemPropertyKey count 1), relation id 1 backward, value 0x01
     ex = np.array([0x02, 0x80, 0x00, 0x01, 0x01], np.uint8)
     order = np.argsort(row, kind="stable")
@@ -69,7 +85,7 @@ def write_edgestore(scale, ef, seed):
     slot = np.ones(2 * m + n, bool)
     slot[pos_exists] = False
     ent_len[pos_exists] = len(ex)
-    ent_len[slot] = elen[order]
+    ent_len[slot] = elen[order] + (10 if f64_key else 0)
     off = np.zeros(2 * m + n + 1, np.int64)
     off[1:] = np.cumsum(ent_len)
     data = np.empty(int(off[-1]), np.uint8)
@@ -83,10 +99,15 @@ def write_edgestore(scale, ef, seed):
     for j in range(rb.shape[1]):
         w = j < rn[order]
         data[(eoff + 1 + on[order] + j)[w]] = rb[order][w, j]
+    if f64_key:
+        for j in range(10):
+            data[eoff + elen[order] + j] = prop[order][:, j]
     vpos = ent_len.astype(np.int32)
+    vpos[slot] = elen[order]
     vpos[pos_exists] = 4
     keys = (vid >> 8) << 3  # IDManager.getKey at 32 partitions: partition 0 in the top bits, count << 3
-    return vid, s, t, keys.astype(np.uint64), row_off, data, off, vpos
+    rel_list = relr[order][dirs[order] == 0]  # the decoder's edge list: the OUT entries in row, then entry order
+    return vid, s, t, keys.astype(np.uint64), row_off, data, off, vpos, rel_list
 
 
 def main():
@@ -95,10 +116,13 @@ def main():
     ap.add_argument("--edgefactor", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chunks", default="1,8,32")
+    ap.add_argument("--relations", action="store_true")
+    ap.add_argument("--f64-key", action="store_true")
     args = ap.parse_args()
     import janusgraph_amd as jg
     t0 = time.perf_counter()
-    vid, s, t, keys, roff, data, off, vpos = write_edgestore(args.scale, args.edgefactor, 0x5EED + args.scale)
+    vid, s, t, keys, roff, data, off, vpos, rel_list = write_edgestore(args.scale, args.edgefactor, 0x5EED + args.scale,
+                                                                      args.f64_key)
     gen_s = time.perf_counter() - t0
     ctx = jg.Context((0,))
     flags = jg.ADJ_IN
@@ -138,16 +162,29 @@ def main():
         for _ in range(args.reps):
             b = ctx.builder()
             b.set_schema()
+            if args.relations:
+                b.keep_relations()
+            if args.f64_key:
+                b.set_weight_key_f64(F64_KEY, [F64_KEY], [jg._lib.PROP_DOUBLE])
+            kflags = flags | (jg._lib.ADJ_EDGE_INDEX if args.relations or args.f64_key else 0)
             t0 = time.perf_counter()
             for p in pieces:
                 b.add_rows(*p)
             t1 = time.perf_counter()
-            gk = b.finish(flags)
+            gk = b.finish(kflags)
             t2 = time.perf_counter()
             st = ctx.stats()
             b.close()
+            nnz = int(gk.info()["num_edges"])  # entries of the one adjacency built (ADJ_IN)
+            extra = ((8 * len(vpos) + 16 * len(rel_list) + 4 * nnz if args.relations else 0) +
+                     (8 * len(vpos) + 16 * len(rel_list) + 12 * nnz if args.f64_key else 0) -
+                     (4 * nnz if args.relations and args.f64_key else 0))  # the ordinals are written once
+            if args.relations:
+                at = np.linspace(0, len(rel_list) - 1, 4096).astype(np.int64)
+                assert np.array_equal(gk.edge_relations(at), rel_list[at]), "relation ids differ from the writer's"
             runs.append({"chunks": k, "add_rows_wall_ms": round((t1 - t0) * 1e3, 2),
-                         "finish_wall_ms": round((t2 - t1) * 1e3, 2),
+                         "finish_wall_ms": round((t2 - t1) * 1e3, 2), "build_ms": round(st["build_ms"], 2),
+                         "opt_in_extra_bytes": int(extra),
                          "copy_ms_sum": round(st["exchange_ms"], 2),
                          "copy_decode_ms_sum": round(st["kernel_ms_total"], 2),
                          "decode_ms_sum": round(st["kernel_ms_total"] - st["exchange_ms"], 2),
@@ -172,6 +209,7 @@ def main():
                             "bytes": alg},
         "entries_per_s_G": round(len(vpos) / (kern_ms * 1e-3) / 1e9, 2),
         "writer_s": round(gen_s, 1), "pagerank_identical": True,
+        "relations": bool(args.relations), "f64_key": bool(args.f64_key),
     }
     print(json.dumps(line), flush=True)
     g_es.close()
