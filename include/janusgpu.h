@@ -85,7 +85,7 @@ extern "C" {
  * jg_graph_set_weights_f64, jg_sssp_keep_f64, jg_sssp_kept_row_f64, jg_sssp_kept_dag_f64,
  * jg_sssp_kept_dag_edges_f64, jg_sssp_kept_dag_read_f64 added; jg_builder_keep_relations,
  * jg_builder_set_weight_key_f64, jg_graph_edge_relations, jg_bfs_kept_dag_read_relations,
- * jg_sssp_kept_dag_read_relations added. */
+ * jg_sssp_kept_dag_read_relations added; jg_builder_keep_scope_ordinals, jg_graph_scope_positions added. */
 #define JG_ABI_VERSION 3
 
 /* ---- status codes ---- */
@@ -117,7 +117,8 @@ extern "C" {
  * ghost-ended edges included.
  * JG_ERR_UNSUPPORTED with the flag: graphs of several shards (logical shards, rank mode); jg_builder_add_rows
  * builders without such an opt-in and jg_graph_build_edgestore (the relation ids the decoder computes are not kept);
- * jg_builder_finish_labels (its select compacts the list); jg_graph_build_rmat (no caller edge list).
+ * jg_builder_finish_labels on a builder without jg_builder_keep_scope_ordinals (its select compacts the list; with
+ * the opt-in the scope's kept list is the edge list); jg_graph_build_rmat (no caller edge list).
  * Without the flag a build is what it was before the flag existed: no allocation, no sort payload, no launch. */
 #define JG_ADJ_EDGE_INDEX 16u
 
@@ -310,7 +311,8 @@ int jg_builder_set_weight_key(jg_builder* b, int64_t weight_key, const int64_t* 
  * with the edge list.  Must precede every chunk (else JG_ERR_STATE); rows only (jg_builder_add_vertices /
  * _add_edges / _add_labeled_edges on such a builder: JG_ERR_ARG); mutually exclusive with a positive
  * jg_builder_set_query_limit, in either order (the second of the two: JG_ERR_STATE); may be combined with
- * jg_builder_keep_labels (jg_builder_finish_labels keeps refusing JG_ADJ_EDGE_INDEX).
+ * jg_builder_keep_labels (jg_builder_finish_labels keeps refusing JG_ADJ_EDGE_INDEX unless the builder also
+ * called jg_builder_keep_scope_ordinals; then the scope's compacted relation table moves into the scoped graph).
  * jg_builder_finish(flags | JG_ADJ_EDGE_INDEX) then succeeds on one shard (several shards, rank mode:
  * JG_ERR_UNSUPPORTED).  The graph's edge list is the decoder's kept list (see JG_ADJ_EDGE_INDEX), ordinals index
  * it, and the relation table (8 B per listed edge, counted in jg_graph_info.device_bytes) moves into the graph.
@@ -376,9 +378,31 @@ int jg_builder_finish(jg_builder* b, uint32_t flags, jg_graph** out);
  * behave as in jg_builder_finish.  Stats: build_ms (the whole call), kernel_ms_total = HIP-event time of
  * the scope select, kernel_launches = the select's own launches (the count, then the scatter if anything is
  * kept; 0 for an empty edge list), algorithmic_bytes = 16 B per accumulated edge (its label read twice) +
- * 2 x 16 B (20 B with weights) per kept edge (read, then written). */
+ * 2 x 16 B (20 B with weights) per kept edge (read, then written).
+ *
+ * Edge ordinals in a scope.  jg_builder_finish_labels(flags | JG_ADJ_EDGE_INDEX) is JG_ERR_UNSUPPORTED (the select
+ * compacts the edge list) unless the builder opted in:
+ * jg_builder_keep_scope_ordinals: must precede every chunk (else JG_ERR_STATE); needs jg_builder_keep_labels, in
+ * either order (checked at jg_builder_finish_labels: JG_ERR_STATE).  A builder that never calls it behaves as before.
+ * With it, jg_builder_finish_labels(flags | JG_ADJ_EDGE_INDEX) succeeds on one shard (several shards, rank mode:
+ * JG_ERR_UNSUPPORTED).  The scoped graph's edge list is the scope's kept list: ordinal k is the k-th kept edge in
+ * accumulated order (the select is a stable compaction), so jg_graph_neighbor_edges, both _kept_dag_edges families
+ * and jg_graph_set_weights_f64 (m = the kept count) behave as on a graph jg_builder_finish built from those edges
+ * alone.  The same scatter pass carries along, per kept edge: its position in the accumulated list (8 B, written
+ * only; the table moves into the graph, counted in jg_graph_info.device_bytes); on a rows builder with
+ * jg_builder_keep_relations its relation id (the compacted table moves into the graph: jg_graph_edge_relations and
+ * the _kept_dag_read_relations calls work; the builder's own table stays for later scopes and a final
+ * jg_builder_finish); on a rows builder with jg_builder_set_weight_key_f64 its decoded double, and the finish then
+ * does what jg_graph_set_weights_f64 does on the scope's doubles only (a NaN on an edge outside the scope is legal; a
+ * bad value inside it: the same error codes, no graph, the builder stays usable).  Without the flag the opt-in
+ * changes nothing.  Stats: algorithmic_bytes grows by 8 B per kept edge for the positions and by 16 B per kept edge
+ * for each of the other two columns; kernel_launches is unchanged.
+ * jg_graph_scope_positions: pos_out[i] = the accumulated-list position of ordinal first + i, for [first, first +
+ * count).  A graph without the table: JG_ERR_UNSUPPORTED; a range outside the list: JG_ERR_ARG; count == 0: JG_OK. */
 #define JG_MAX_SCOPE_LABELS 1024
 int jg_builder_keep_labels(jg_builder* b);
+int jg_builder_keep_scope_ordinals(jg_builder* b);
+int jg_graph_scope_positions(const jg_graph* g, int64_t first, int64_t count, int64_t* pos_out);
 int jg_builder_add_labeled_edges(jg_builder* b, const int64_t* src, const int64_t* dst, const int32_t* weight,
                                  const int64_t* label, int64_t m);
 int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabels, uint32_t flags, jg_graph** out);

@@ -59,6 +59,7 @@ EXPORTS = [
     "jg_sssp_kept_dag_edges_f64", "jg_sssp_kept_dag_read_f64",
     "jg_builder_keep_relations", "jg_builder_set_weight_key_f64", "jg_graph_edge_relations",
     "jg_bfs_kept_dag_read_relations", "jg_sssp_kept_dag_read_relations",
+    "jg_builder_keep_scope_ordinals", "jg_graph_scope_positions",
 ]
 # JG_PROP_* property value types (jg_builder_set_weight_key)
 PROP_BYTE, PROP_SHORT, PROP_INT, PROP_LONG, PROP_CHAR, PROP_BOOL, PROP_DATE, PROP_FLOAT, PROP_DOUBLE, PROP_UUID, \
@@ -236,6 +237,8 @@ def load():
         "jg_graph_edge_relations": ([_P, _P, _i64, _P], ctypes.c_int),
         "jg_bfs_kept_dag_read_relations": ([_P, _i64, _i64, _P], ctypes.c_int),
         "jg_sssp_kept_dag_read_relations": ([_P, _i64, _i64, _P], ctypes.c_int),
+        "jg_builder_keep_scope_ordinals": ([_P], ctypes.c_int),
+        "jg_graph_scope_positions": ([_P, _i64, _i64, _P], ctypes.c_int),
         "jg_sssp_keep_f64": ([_P, _i64, _i32], ctypes.c_int),
         "jg_sssp_kept_row_f64": ([_P, _P], ctypes.c_int),
         "jg_sssp_kept_dag_f64": ([_P, _P, ctypes.c_double, _P, _P, _P], ctypes.c_int),
@@ -453,6 +456,12 @@ class Builder:
         (before the first chunk; rows only; not under a positive query limit).  finish(flags | ADJ_EDGE_INDEX)
         then numbers the decoder's edge list and Graph.edge_relations names each ordinal's relation."""
         check(load().jg_builder_keep_relations(self._h))
+
+    def keep_scope_ordinals(self):
+        """jg_builder_keep_scope_ordinals: let finish_labels(labels, flags | ADJ_EDGE_INDEX) number a scope's edges
+        (before the first chunk; needs keep_labels, in either order).  Ordinal k is the scope's k-th kept edge, and
+        Graph.scope_positions names its position in the accumulated list."""
+        check(load().jg_builder_keep_scope_ordinals(self._h))
 
     def add_edges(self, src, dst, weight=None, label=None):
         """jg_builder_add_edges, or with `label` (one int64 per edge) jg_builder_add_labeled_edges."""
@@ -915,6 +924,17 @@ class Graph:
         rel = np.empty(max(len(o), 1), np.int64)
         check(load().jg_graph_edge_relations(self._h, _ptr(o), len(o), _ptr(rel)))
         return rel[:len(o)]
+
+    def scope_positions(self, first=0, count=None):
+        """jg_graph_scope_positions: the accumulated-list positions (int64) of the scope's edge ordinals
+        [first, first + count), all from `first` on by default (a graph of a Builder.keep_scope_ordinals builder,
+        finish_labels with ADJ_EDGE_INDEX)."""
+        if count is None:
+            i = self.info()  # the listed edges: the scope's kept edges, ghost-ended ones included
+            count = max(i["num_edges"] + i["ghost_edges"] - int(first), 0)
+        pos = np.empty(max(int(count), 1), np.int64)
+        check(load().jg_graph_scope_positions(self._h, int(first), int(count), _ptr(pos)))
+        return pos[:max(int(count), 0)]
 
     def neighbors(self, rows, direction=DIR_BOTH):
         """jg_graph_neighbors: (off, nbr) CSR of the given output-order rows, in output-order indices."""

@@ -235,7 +235,7 @@ class GpuGraphComputer:
             return vid, props, vp.max_depth, {}
         if isinstance(vp, ConnectedComponentVertexProgram):
             vid, src, dst, _ = g0.snapshot()
-            g = ctx.build(vid, src, dst, flags=_lib.ADJ_BOTH)
+            g = self._program_graph(ctx, vid, src, dst, vp.edge_labels, _lib.ADJ_BOTH)
             try:
                 if self._census_route(vp) and g.info()["num_shards"] == 1:
                     # the map-reduces only group the labels: the census is made on the device
@@ -253,7 +253,8 @@ class GpuGraphComputer:
         if isinstance(vp, PeerPressureVertexProgram):
             vid, src, dst, _ = g0.snapshot()
             direction = PeerPressureVertexProgram.SCOPES[vp.edges]
-            g = ctx.build(vid, src, dst, flags=_lib.ADJ_IN if direction == _lib.DIR_OUT else _lib.ADJ_BOTH)
+            g = self._program_graph(ctx, vid, src, dst, vp.edge_labels,
+                                    _lib.ADJ_IN if direction == _lib.DIR_OUT else _lib.ADJ_BOTH)
             try:
                 if g.info()["num_shards"] != 1:
                     # jg_peer_pressure runs on one shard: the Java side keeps delegating
@@ -270,10 +271,7 @@ class GpuGraphComputer:
             vid, src, dst, _ = g0.snapshot()
             direction = CombinerVertexProgram.SCOPES[vp.scope]
             adj = {_lib.DIR_OUT: _lib.ADJ_OUT, _lib.DIR_IN: _lib.ADJ_IN, _lib.DIR_BOTH: _lib.ADJ_BOTH}[direction]
-            if vp.labels is None:
-                g = ctx.build(vid, src, dst, flags=adj)
-            else:
-                g = self._label_scoped_graph(ctx, vid, src, dst, vp.labels, adj)
+            g = self._program_graph(ctx, vid, src, dst, vp.labels, adj)
             try:
                 x, received = g.combine_steps(direction, CombinerVertexProgram.COMBINERS.index(vp.combiner), vp.length,
                                               np.full(len(vid), vp.initial_message, np.int64), vp.int32)
@@ -300,21 +298,64 @@ class GpuGraphComputer:
         return (self.persist_mode is Persist.NOTHING and bool(self.map_reduces)
                 and all(type(mr) is PageRankTopMapReduce for mr in self.map_reduces))
 
-    def _label_scoped_graph(self, ctx, vid, src, dst, labels, flags):
-        """The snapshot through a label-keeping builder, cut down to the typed scope's labels on the GPU
-        (jg_builder_finish_labels).  A name the graph does not know gets an id no edge has: it matches
-        nothing, as BasicVertexCentricQueryBuilder.java:484 skips unknown types."""
+    def _edge_scope(self, labels):
+        """A label scope over snapshot()'s edge list, worked out once per run: (label id per edge, the scope's label
+        ids, one flag per edge: the edge is in the scope); None for labels None (every edge).  A name the graph does
+        not know gets an id no edge has, so it matches nothing, as BasicVertexCentricQueryBuilder.java:484 skips
+        unknown types."""
+        if labels is None:
+            return None
         lab, ids = self.graph.edge_label_ids()
         unknown = len(ids)
-        scope = [ids.get(name, unknown) for name in labels]
+        scope_ids = [ids.get(name, unknown) for name in labels]
+        return lab, scope_ids, np.isin(lab, scope_ids)
+
+    def _scope_weights(self, key, scope, float_weights):
+        """snapshot() with the weight column of property `key`, and the flags of the edges the weight checks cover.
+        Under a label scope only the scope's edges are read; the others count as edges without the property (their
+        values may be anything)."""
+        if scope is None:
+            vid, src, dst, w = self.graph.snapshot(weight_property=key, float_weights=float_weights)
+            return vid, src, dst, w, np.ones(len(w), bool)
+        vid, src, dst, _ = self.graph.snapshot()
+        absent = float("nan") if float_weights else int(_lib.WEIGHT_ABSENT)
+        cast = float if float_weights else int
+        w = np.asarray([cast(e.properties[key]) if k and key in e.properties else absent
+                        for e, k in zip(self.graph.edges, scope[2].tolist())],
+                       dtype=np.float64 if float_weights else np.int32)
+        return vid, src, dst, w, scope[2]
+
+    def _label_scoped_graph(self, ctx, vid, src, dst, scope, flags, weight=None, numbered=False):
+        """The snapshot through a label-keeping builder, cut down to the labels of `scope` (_edge_scope) on the GPU
+        (jg_builder_finish_labels); `weight`: the edges' int32 weights, which travel through the select.
+        Returns (graph, pos).  numbered: the builder keeps scope ordinals and `flags` carries ADJ_EDGE_INDEX, so
+        the scope's k-th kept edge has ordinal k, and pos[k] (Graph.scope_positions) is its position in
+        snapshot()'s edge list: a path's Edge objects are graph.edges[pos[ordinal]], the doubles handed to
+        set_weights_f64 are w[pos].  Not numbered: pos is None."""
+        lab, scope_ids, _ = scope
         b = ctx.builder()
         try:
             b.keep_labels()
+            if numbered:
+                b.keep_scope_ordinals()
             b.add_vertices(vid)
-            b.add_edges(src, dst, label=lab)
-            return b.finish_labels(scope, flags)
+            b.add_edges(src, dst, weight=weight, label=lab)
+            g = b.finish_labels(scope_ids, flags | (_lib.ADJ_EDGE_INDEX if numbered else 0))
         finally:
             b.close()
+        if not numbered:
+            return g, None
+        try:
+            return g, g.scope_positions()
+        except BaseException:
+            g.close()
+            raise
+
+    def _program_graph(self, ctx, vid, src, dst, labels, flags, weight=None):
+        """The graph a program runs on: every edge (labels None), or the label scope's edges only."""
+        if labels is None:
+            return ctx.build(vid, src, dst, weight, flags=flags)
+        return self._label_scoped_graph(ctx, vid, src, dst, self._edge_scope(labels), flags, weight)[0]
 
     def _shortest_paths(self, ctx, vp):
         """ShortestPaths.execute: 64 sources per bit-parallel pass.  On one shard the depth rows stay on the
@@ -338,17 +379,20 @@ class GpuGraphComputer:
         sources, target = _path_endpoints(vp, vid)
         both = direction == _lib.DIR_BOTH
         flags = _lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT
-        if vp.include_edges:
-            flags |= _lib.ADJ_EDGE_INDEX
+        pos = None  # a numbered label scope: the snapshot position of each of its edge ordinals
         try:
-            g = ctx.build(vid, src, dst, flags=flags)
+            if vp.edge_labels is not None:
+                g, pos = self._label_scoped_graph(ctx, vid, src, dst, self._edge_scope(vp.edge_labels), flags,
+                                                  numbered=vp.include_edges)
+            else:
+                g = ctx.build(vid, src, dst, flags=flags | (_lib.ADJ_EDGE_INDEX if vp.include_edges else 0))
         except _lib.JanusGpuError as e:
             if vp.include_edges and e.code == _lib.JG_ERR_UNSUPPORTED:
                 # ordinals are kept on one shard only (JG_ADJ_EDGE_INDEX): the Java side keeps delegating
                 raise ProgramNotSupported("ShortestPathVertexProgram with includeEdges is not run on a sharded "
                                           "graph; delegate to FulgoraGraphComputer") from e
             raise
-        edges = self.graph.edges
+        edges = self.graph.edges if pos is None else [self.graph.edges[k] for k in pos.tolist()]
         paths, max_level = [], 0
         max_depth = _int_bound(vp.max_distance)
         try:
@@ -390,19 +434,25 @@ class GpuGraphComputer:
         max_level + 1 means on the hop route; this project's rule, not pinned by any reference test."""
         direction = _PATH_DIRECTIONS[vp.edge_direction]
         key = vp.distance_property
-        if any(isinstance(e.properties.get(key), (float, np.floating)) for e in self.graph.edges):
-            return self._f64_shortest_paths(ctx, vp)
-        vid, src, dst, w = self.graph.snapshot(weight_property=vp.distance_property)
-        if len(w) and int(w.min()) < 1:
-            missing = int((w == _lib.WEIGHT_ABSENT).sum())
+        scope = self._edge_scope(vp.edge_labels)
+        inside = self.graph.edges if scope is None else [e for e, k in zip(self.graph.edges, scope[2].tolist()) if k]
+        if any(isinstance(e.properties.get(key), (float, np.floating)) for e in inside):
+            return self._f64_shortest_paths(ctx, vp, scope, inside)
+        vid, src, dst, w, checked = self._scope_weights(key, scope, False)
+        ws = w[checked]  # the checks cover the scope's edges only
+        if len(ws) and int(ws.min()) < 1:
+            missing = int((ws == _lib.WEIGHT_ABSENT).sum())
             raise ProgramNotSupported(
                 f"ShortestPathVertexProgram with distanceProperty {vp.distance_property!r} is not run by "
                 f"GpuGraphComputer: " + (f"{missing} edge(s) lack the property" if missing else
                                          "an edge has a weight < 1") + "; delegate to FulgoraGraphComputer")
         sources, target = _path_endpoints(vp, vid)
         both = direction == _lib.DIR_BOTH
-        g = ctx.build(vid, src, dst, w, flags=(_lib.ADJ_BOTH | _lib.ADJ_WEIGHT_BOTH) if both
-                      else _lib.ADJ_IN | _lib.ADJ_OUT)
+        flags = (_lib.ADJ_BOTH | _lib.ADJ_WEIGHT_BOTH) if both else _lib.ADJ_IN | _lib.ADJ_OUT
+        if scope is None:
+            g = ctx.build(vid, src, dst, w, flags=flags)
+        else:
+            g, _ = self._label_scoped_graph(ctx, vid, src, dst, scope, flags, w)
         paths, longest = [], 0
         max_distance = _int_bound(vp.max_distance)
         try:
@@ -419,7 +469,7 @@ class GpuGraphComputer:
             g.close()
         return vid, {}, longest + 1, {vp.SHORTEST_PATHS: paths}
 
-    def _f64_shortest_paths(self, ctx, vp):
+    def _f64_shortest_paths(self, ctx, vp, scope, inside):
         """_weighted_shortest_paths when an edge's value for the key is a float (a Double property): a path's
         length is the IEEE binary64 sum of its weights, ties are exact (jg_graph_set_weights_f64,
         jg_sssp_keep_f64, jg_sssp_kept_dag_f64).  Every value must be a Python / numpy int (converted exactly;
@@ -433,7 +483,7 @@ class GpuGraphComputer:
             return ProgramNotSupported(f"ShortestPathVertexProgram with distanceProperty {key!r} is not run by "
                                        f"GpuGraphComputer: {why}; delegate to FulgoraGraphComputer")
 
-        for e in self.graph.edges:
+        for e in inside:  # the edges of the label scope `scope` (_edge_scope): the checks cover them only
             x = e.properties.get(key)
             if x is None:
                 raise refuse("an edge lacks the property")
@@ -442,13 +492,19 @@ class GpuGraphComputer:
             if isinstance(x, (int, np.integer)) and abs(int(x)) > 2**53:
                 raise refuse("an integer beyond 2^53 has no exact double")
         direction = _PATH_DIRECTIONS[vp.edge_direction]
-        vid, src, dst, w = self.graph.snapshot(weight_property=key, float_weights=True)
-        if len(w) and not (np.isfinite(w).all() and w.min() > 0):
+        vid, src, dst, w, checked = self._scope_weights(key, scope, True)
+        ws = w[checked]
+        if len(ws) and not (np.isfinite(ws).all() and ws.min() > 0):
             raise refuse("a weight is not finite and > 0")
         sources, target = _path_endpoints(vp, vid)
         both = direction == _lib.DIR_BOTH
+        flags = _lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT
         try:
-            g = ctx.build(vid, src, dst, flags=(_lib.ADJ_BOTH if both else _lib.ADJ_IN | _lib.ADJ_OUT) | _lib.ADJ_EDGE_INDEX)
+            if scope is not None:  # the scope's doubles, in its ordinals' order
+                g, pos = self._label_scoped_graph(ctx, vid, src, dst, scope, flags, numbered=True)
+                w = w[pos]
+            else:
+                g = ctx.build(vid, src, dst, flags=flags | _lib.ADJ_EDGE_INDEX)
         except _lib.JanusGpuError as e:
             if e.code == _lib.JG_ERR_UNSUPPORTED:  # edge ordinals are kept on one shard only
                 raise refuse("the graph is sharded") from e

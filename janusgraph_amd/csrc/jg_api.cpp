@@ -648,6 +648,8 @@ struct jg_builder {
     bool keep_relations = false;  // jg_builder_keep_relations: rows only, a relation id beside every edge (dec->rel)
     bool keep_labels = false;  // jg_builder_keep_labels: a label beside every edge (ids: lab; rows: dec->lab)
     bool sealed = false;       // after the first jg_builder_finish_labels: no more chunks
+    // jg_builder_keep_scope_ordinals: jg_builder_finish_labels numbers a scope's edges (JG_ADJ_EDGE_INDEX)
+    bool keep_scope_ordinals = false;
     jg::DevBuf<int64_t> lab;
     int64_t ml = 0;
 };
@@ -1129,6 +1131,15 @@ int jg_builder_keep_labels(jg_builder* b) {
     JG_GUARD_END
 }
 
+int jg_builder_keep_scope_ordinals(jg_builder* b) {
+    JG_GUARD_BEGIN
+    JG_ARG(b, "null builder");
+    if (b->finished || b->sealed || b->mode != 0)
+        jg::fail(JG_ERR_STATE, "jg_builder_keep_scope_ordinals must precede every chunk");
+    b->keep_scope_ordinals = true;
+    JG_GUARD_END
+}
+
 int jg_builder_keep_relations(jg_builder* b) {
     JG_GUARD_BEGIN
     JG_ARG(b, "null builder");
@@ -1330,7 +1341,9 @@ int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabe
     JG_ARG(weight_both_ok(flags, b->mode == 2 ? (b->dec && b->dec->weighted == 1) : b->weights == 1), kWeightBothRule);
     if (b->finished) jg::fail(JG_ERR_STATE, "builder already finished");
     if (!b->keep_labels) jg::fail(JG_ERR_STATE, "jg_builder_finish_labels needs jg_builder_keep_labels before the first chunk");
-    edge_index_check(flags, *b->ctx, "a label scope's select compacts the edge list");
+    // a scope numbers its edges (ordinal k: the k-th kept edge) only on a builder that opted in
+    edge_index_check(flags, *b->ctx, b->keep_scope_ordinals ? nullptr : "a label scope's select compacts the edge list");
+    const bool numbered = b->keep_scope_ordinals && (flags & JG_ADJ_EDGE_INDEX);
     static_assert(JG_MAX_SCOPE_LABELS == jg::kScopeMaxLabels, "the header's cap is the select's");
     std::vector<int64_t> set;
     switch (jg::label_set_prepare(labels, nlabels, set)) {
@@ -1355,9 +1368,13 @@ int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabe
         const int64_t *vid, *src, *dst, *lab;
         const int32_t* w = nullptr;
         int64_t n, m;
+        jg::ScopeCols cols;
         if (b->mode == 2) {
             jg::EdgestoreDecoder& d = *b->dec;
             d.finish();
+            // the builder's own tables stay: a later scope or a final jg_builder_finish reads them again
+            if (numbered && d.keep_relations() && d.m > 0) cols.rel = d.rel.get();
+            if (numbered && d.weight_f64() && d.m > 0) cols.wf = d.wf.get();
             if (d.vid.size() == 0) d.vid.alloc(1);
             vid = d.vid.get();
             n = d.n;
@@ -1380,8 +1397,26 @@ int jg_builder_finish_labels(jg_builder* b, const int64_t* labels, int32_t nlabe
         jg::DevBuf<int64_t> ssrc, sdst;
         jg::DevBuf<int32_t> sw;
         hipStream_t s = builder_stream(b);
-        sel = jg::scope_select(lab, src, dst, w, m, set, ssrc, sdst, sw, s);
+        sel = jg::scope_select(lab, src, dst, w, m, set, ssrc, sdst, sw, s, numbered ? &cols : nullptr);
         jg::build_from_device_ids(g, dev0, s, vid, n, ssrc.get(), sdst.get(), w ? sw.get() : nullptr, sel.kept);
+        if (numbered) {
+            // the scope's doubles only: a NaN on an edge outside the scope is legal (statistics, gate and gather as
+            // jg_graph_set_weights_f64 does them; a bad value throws before anything below is kept)
+            if (b->mode == 2 && b->dec->weight_f64()) {
+                if (cols.owf.size() == 0) cols.owf.alloc(1);
+                jg::graph_set_weights_f64_device(g, cols.owf.get(), sel.kept,
+                                                 "jg_builder_finish_labels (jg_builder_set_weight_key_f64)");
+            }
+            g.scope_pos.swap(cols.opos);
+            g.has_scope_pos = true;
+            g.info.device_bytes += 8 * sel.kept;
+            if (b->mode == 2 && b->dec->keep_relations()) {
+                if (cols.orel.size() == 0) cols.orel.alloc(1);
+                g.edge_rel.swap(cols.orel);
+                g.has_edge_rel = true;
+                g.info.device_bytes += 8 * sel.kept;
+            }
+        }
     }
     const float ms = timer.stop();
     c.last = jg_stats{};
@@ -1748,6 +1783,24 @@ int jg_sssp_kept_dag_read_relations(jg_graph* g, int64_t first, int64_t count, i
     JG_GUARD_BEGIN
     JG_ARG(g, "null graph");
     jg::sssp_kept_dag_read_relations(g->impl, first, count, rel_out);
+    JG_GUARD_END
+}
+
+int jg_graph_scope_positions(const jg_graph* g, int64_t first, int64_t count, int64_t* pos_out) {
+    JG_GUARD_BEGIN
+    JG_ARG(g, "null graph");
+    const jg::Graph& gr = g->impl;
+    if (!gr.has_scope_pos)
+        jg::fail(JG_ERR_UNSUPPORTED, "the graph holds no scope positions (jg_builder_keep_scope_ordinals, then "
+                                     "jg_builder_finish_labels with JG_ADJ_EDGE_INDEX)");
+    JG_ARG(first >= 0 && count >= 0 && first <= gr.edge_list_m && count <= gr.edge_list_m - first,
+           "range outside the scope's edge list");
+    JG_ARG(count == 0 || pos_out, "pos_out is null");
+    if (count > 0) {
+        const jg::Shard& sh = *gr.shards[0];
+        jg::DeviceGuard dg(sh);
+        jg::copy_d2h(pos_out, gr.scope_pos.get() + first, (size_t)count * sizeof(int64_t), sh.stream);
+    }
     JG_GUARD_END
 }
 

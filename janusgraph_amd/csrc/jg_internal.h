@@ -343,6 +343,10 @@ struct Graph {
     // edge_rel[ordinal] for ordinals [0, edge_list_m), on the first shard's device (counted in info.device_bytes)
     bool has_edge_rel = false;
     DevBuf<int64_t> edge_rel;
+    // jg_builder_keep_scope_ordinals + jg_builder_finish_labels(JG_ADJ_EDGE_INDEX): the position in the builder's
+    // accumulated list of every listed (kept) edge, scope_pos[ordinal], beside edge_rel and counted the same way
+    bool has_scope_pos = false;
+    DevBuf<int64_t> scope_pos;
     // jg_graph_set_weights_f64: the double weights are set (Csr::wf beside every built adjacency), and their
     // smallest, largest and mean value (a fixed-order reduction: the same bits on every run)
     bool has_wf = false;
@@ -601,9 +605,19 @@ struct ScopeSelect {
     int64_t launches = 0;  // its kernel launches
     double bytes = 0;      // its byte model: labels twice, the kept payload in and out
 };
+// A numbered scope's extra columns (jg_builder_keep_scope_ordinals; nullable cols: the plain select).  The same
+// scatter writes, beside every kept edge, its position in the accumulated list (opos, always) and, where the
+// accumulated column is given, its relation id (rel -> orel) and its decoded double (wf -> owf); each is
+// allocated here (at least one element) and fully written for [0, kept).
+struct ScopeCols {
+    const int64_t* rel = nullptr;
+    const double* wf = nullptr;
+    DevBuf<int64_t> opos, orel;
+    DevBuf<double> owf;
+};
 ScopeSelect scope_select(const int64_t* lab, const int64_t* src, const int64_t* dst, const int32_t* w, int64_t m,
                          const std::vector<int64_t>& set, DevBuf<int64_t>& osrc, DevBuf<int64_t>& odst,
-                         DevBuf<int32_t>& ow, hipStream_t s);
+                         DevBuf<int32_t>& ow, hipStream_t s, ScopeCols* cols = nullptr);
 
 // ---- programs ----
 void pagerank_begin(Graph& g, double damping, int64_t vertex_count);

@@ -10,6 +10,8 @@
 // flight together), so the order of the kept edges is wave-major, then run, then lane: the rank inside a
 // run is popcount(ballot & lanemask_lt), the runs of a wave add up in registers (the ballots are
 // wave-uniform), and the waves of a block are ranked by block_exclusive_scan_add.  64-bit indices.
+// A numbered scope (jg_builder_keep_scope_ordinals) takes up to three 8-byte columns along in the same scatter:
+// each kept edge's position in the accumulated list, its relation id and its decoded double (ScopeCols).
 #include "jg_internal.h"
 #include "jg_labelset.h"
 #include "jg_prim.h"
@@ -78,7 +80,12 @@ __global__ __launch_bounds__(kBlock) void scope_count_kernel(const int64_t* __re
     }
 }
 
-template <bool kWeights>
+// kCols: the numbered scope's flavour.  Its columns are each optional (a null output: not asked for; the checks
+// are kernel arguments, so wave-uniform).  A column is loaded and stored in a phase of its own behind src / dst /
+// w, reusing the flags and ranks.  The compiler hoists the later phases' loads above the earlier stores, so the
+// flavour does hold more live values than the plain one: 114 / 122 VGPRs against 67 / 75 (no scratch; 4 waves per
+// SIMD against 7 / 6).  The plain flavours' code is what it was.
+template <bool kWeights, bool kCols>
 __global__ __launch_bounds__(kBlock) void scope_scatter_kernel(const int64_t* __restrict__ lab,
                                                                 const int64_t* __restrict__ src,
                                                                 const int64_t* __restrict__ dst,
@@ -86,7 +93,12 @@ __global__ __launch_bounds__(kBlock) void scope_scatter_kernel(const int64_t* __
                                                                 const int64_t* __restrict__ set, int nset,
                                                                 int64_t ntiles, const int64_t* __restrict__ tile_off,
                                                                 int64_t kept, int64_t* __restrict__ osrc,
-                                                                int64_t* __restrict__ odst, int32_t* __restrict__ ow) {
+                                                                int64_t* __restrict__ odst, int32_t* __restrict__ ow,
+                                                                const int64_t* __restrict__ rel,
+                                                                const double* __restrict__ wf,
+                                                                int64_t* __restrict__ opos,
+                                                                int64_t* __restrict__ orel,
+                                                                double* __restrict__ owf) {
     __shared__ int64_t lds_set[kScopeMaxLabels];
     __shared__ uint32_t scan_scratch[kBlock / kWave];
     stage_label_set(set, nset, lds_set);
@@ -138,6 +150,37 @@ __global__ __launch_bounds__(kBlock) void scope_scatter_kernel(const int64_t* __
                 if (kWeights) ow[o] = c[j];
             }
         }
+        if (kCols) {
+            if (opos) {
+#pragma unroll
+                for (int j = 0; j < kScopeEpt; ++j) {
+                    const int64_t o = out0 + rank[j];
+                    if (f[j] && o < kept) opos[o] = base + (int64_t)j * kWave;
+                }
+            }
+            if (orel) {
+                int64_t r[kScopeEpt];
+#pragma unroll
+                for (int j = 0; j < kScopeEpt; ++j)
+                    if (f[j]) r[j] = rel[base + (int64_t)j * kWave];
+#pragma unroll
+                for (int j = 0; j < kScopeEpt; ++j) {
+                    const int64_t o = out0 + rank[j];
+                    if (f[j] && o < kept) orel[o] = r[j];
+                }
+            }
+            if (owf) {
+                double d[kScopeEpt];
+#pragma unroll
+                for (int j = 0; j < kScopeEpt; ++j)
+                    if (f[j]) d[j] = wf[base + (int64_t)j * kWave];
+#pragma unroll
+                for (int j = 0; j < kScopeEpt; ++j) {
+                    const int64_t o = out0 + rank[j];
+                    if (f[j] && o < kept) owf[o] = d[j];
+                }
+            }
+        }
     }
 }
 
@@ -145,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void scope_scatter_kernel(const int64_t* __
 
 ScopeSelect scope_select(const int64_t* lab, const int64_t* src, const int64_t* dst, const int32_t* w, int64_t m,
                          const std::vector<int64_t>& set, DevBuf<int64_t>& osrc, DevBuf<int64_t>& odst,
-                         DevBuf<int32_t>& ow, hipStream_t s) {
+                         DevBuf<int32_t>& ow, hipStream_t s, ScopeCols* cols) {
     if (set.empty() || (int64_t)set.size() > kScopeMaxLabels) fail(JG_ERR_ARG, "label set outside [1, JG_MAX_SCOPE_LABELS]");
     ScopeSelect r;
     if (m > 0) {
@@ -173,13 +216,26 @@ ScopeSelect scope_select(const int64_t* lab, const int64_t* src, const int64_t* 
             osrc.alloc((size_t)kept);
             odst.alloc((size_t)kept);
             if (w) ow.alloc((size_t)kept);
+            if (cols) {
+                cols->opos.alloc((size_t)kept);
+                if (cols->rel) cols->orel.alloc((size_t)kept);
+                if (cols->wf) cols->owf.alloc((size_t)kept);
+            }
             JG_HIP(hipEventRecord(t2, s));
-            if (w)
-                scope_scatter_kernel<true><<<grid, kBlock, 0, s>>>(lab, src, dst, w, m, d_set.get(), nset, ntiles,
-                                                                  tile_off.get(), kept, osrc.get(), odst.get(), ow.get());
-            else
-                scope_scatter_kernel<false><<<grid, kBlock, 0, s>>>(lab, src, dst, nullptr, m, d_set.get(), nset, ntiles,
-                                                                   tile_off.get(), kept, osrc.get(), odst.get(), nullptr);
+            const auto launch = [&](auto kernel) {
+                kernel<<<grid, kBlock, 0, s>>>(lab, src, dst, w, m, d_set.get(), nset, ntiles, tile_off.get(), kept,
+                                               osrc.get(), odst.get(), w ? ow.get() : nullptr, cols ? cols->rel : nullptr,
+                                               cols ? cols->wf : nullptr, cols ? cols->opos.get() : nullptr,
+                                               cols && cols->rel ? cols->orel.get() : nullptr,
+                                               cols && cols->wf ? cols->owf.get() : nullptr);
+            };
+            if (cols) {
+                if (w) launch(scope_scatter_kernel<true, true>);
+                else launch(scope_scatter_kernel<false, true>);
+            } else {
+                if (w) launch(scope_scatter_kernel<true, false>);
+                else launch(scope_scatter_kernel<false, false>);
+            }
             JG_LAUNCH_CHECK();
             r.launches = 2;
             JG_HIP(hipEventRecord(t3, s));
@@ -190,6 +246,13 @@ ScopeSelect scope_select(const int64_t* lab, const int64_t* src, const int64_t* 
         }
         const double payload = w ? 20.0 : 16.0;
         r.bytes = 16.0 * (double)m + 2.0 * payload * (double)kept;
+        // a numbered scope: positions are written only (8 B), a relation id or a double is read and written (16 B)
+        if (cols) r.bytes += (8.0 + (cols->rel ? 16.0 : 0.0) + (cols->wf ? 16.0 : 0.0)) * (double)kept;
+    }
+    if (cols) {
+        if (cols->opos.size() == 0) cols->opos.alloc(1);
+        if (cols->rel && cols->orel.size() == 0) cols->orel.alloc(1);
+        if (cols->wf && cols->owf.size() == 0) cols->owf.alloc(1);
     }
     if (osrc.size() == 0) osrc.alloc(1);
     if (odst.size() == 0) odst.alloc(1);

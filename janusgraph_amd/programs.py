@@ -43,6 +43,26 @@ class VertexProgram:
         return []
 
 
+EDGE_LABELS = "edgeLabels"  # configuration key of the label-scoped programs (a tuple of label names, or None)
+
+
+def _edge_labels(labels):
+    """The `edgeLabels` configuration value as a tuple of label names (None: every edge): a program's edges named
+    by label, the bothE("knows") of ShortestPath.edges / ConnectedComponent.edges / PeerPressure's by().  As
+    CombinerVertexProgram.labels: at least one name, every name a string; an empty name is refused too."""
+    if labels is None:
+        return None
+    if isinstance(labels, str):
+        labels = (labels,)
+    try:
+        labels = tuple(labels)
+    except TypeError:
+        raise ValueError("edgeLabels must name at least one edge label") from None
+    if not labels or not all(isinstance(x, str) and x for x in labels):
+        raise ValueError("edgeLabels must name at least one edge label, each a non-empty string")
+    return labels
+
+
 class _Builder:
     def __init__(self, cls):
         self.cls = cls
@@ -50,6 +70,14 @@ class _Builder:
 
     def create(self, graph=None):
         return self.cls(self.configuration)
+
+
+class _LabelScopedBuilder(_Builder):
+    """The builder of a program whose edges may be named by label (the `edgeLabels` key)."""
+
+    def edgeLabels(self, *names):  # noqa: N802
+        self.configuration[EDGE_LABELS] = _edge_labels(names)
+        return self
 
 
 class PageRankVertexProgram(VertexProgram):
@@ -132,8 +160,11 @@ class ConnectedComponentVertexProgram(VertexProgram):
         self.max_iterations = int(conf.get(self.MAX_ITERATIONS, 100))
         if self.max_iterations != 100:
             raise ValueError("GpuGraphComputer runs ConnectedComponentVertexProgram with maxIterations = 100")
+        # edgeLabels (None: every edge): connectedComponent().with(ConnectedComponent.edges, bothE("knows")); only
+        # edges of those labels join vertices, a name the graph does not know matches nothing
+        self.edge_labels = _edge_labels(conf.get(EDGE_LABELS))
 
-    class Builder(_Builder):
+    class Builder(_LabelScopedBuilder):
         def __init__(self):
             super().__init__(ConnectedComponentVertexProgram)
 
@@ -158,7 +189,11 @@ class ShortestPathVertexProgram(VertexProgram):
 
     includeEdges(True) returns each path as [vid, Edge, vid, ..., vid], the Edge objects being the graph's own:
     two parallel edges between the same vertices give two paths.  It runs on the hop route only; together
-    with a distanceProperty it is refused (ValueError)."""
+    with a distanceProperty it is refused (ValueError).
+
+    edgeLabels("knows", ...) (the `edgeLabels` key; None: every edge) names the edges a path may follow, the
+    bothE("knows") of ShortestPath.edges: honoured on every route, and the weight checks of a distanceProperty
+    then cover the named edges only.  A name the graph does not know matches nothing."""
 
     SHORTEST_PATHS = "gremlin.shortestPathVertexProgram.shortestPaths"
     EDGE_DIRECTIONS = ("out", "in", "both")
@@ -178,8 +213,9 @@ class ShortestPathVertexProgram(VertexProgram):
         self.edge_direction = conf.get("edgeDirection", "both")
         if self.edge_direction not in self.EDGE_DIRECTIONS:
             raise ValueError('edgeDirection must be "out", "in" or "both"')
+        self.edge_labels = _edge_labels(conf.get(EDGE_LABELS))
 
-    class Builder(_Builder):
+    class Builder(_LabelScopedBuilder):
         def __init__(self):
             super().__init__(ShortestPathVertexProgram)
 
@@ -383,7 +419,8 @@ class PeerPressureVertexProgram(VertexProgram):
     vote strength among its own vote and the votes it receives; with distributeVote a vertex's strength is
     1 / (edges it votes along).  Votes travel along `edges` ("outE", the default, or "bothE").  The stored
     cluster is the Long id of a vertex.  Among exactly tied clusters GpuGraphComputer takes the numerically
-    smallest id (TinkerPop's choice follows HashMap order and is not defined)."""
+    smallest id (TinkerPop's choice follows HashMap order and is not defined).  edgeLabels("knows", ...) (the
+    `edgeLabels` key; None: every edge) names the edges votes travel along, as peerPressure().by(outE("knows"))."""
 
     CLUSTER = PEER_PRESSURE_CLUSTER
     VOTE_STRENGTH = "gremlin.peerPressureVertexProgram.voteStrength"
@@ -406,8 +443,9 @@ class PeerPressureVertexProgram(VertexProgram):
         if self.edges not in self.SCOPES:
             raise ValueError(f"GpuGraphComputer runs PeerPressureVertexProgram over outE or bothE, not {self.edges!r}")
         self.compute_keys = (self.property, self.VOTE_STRENGTH)
+        self.edge_labels = _edge_labels(conf.get(EDGE_LABELS))
 
-    class Builder(_Builder):
+    class Builder(_LabelScopedBuilder):
         def __init__(self):
             super().__init__(PeerPressureVertexProgram)
 
